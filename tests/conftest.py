@@ -5,6 +5,17 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
+# Strategies, logs, traces and graph dumps go to a per-session scratch dir
+# (set before autodist_amd.const is imported; subprocesses inherit it), not
+# the fixed system-wide default, which another user may own.
+if "AUTODIST_WORKING_DIR" not in os.environ:
+    import atexit
+    import shutil
+    import tempfile
+    _workdir = tempfile.mkdtemp(prefix="autodist_amd_test_")
+    os.environ["AUTODIST_WORKING_DIR"] = _workdir
+    atexit.register(shutil.rmtree, _workdir, ignore_errors=True)
+
 
 def pytest_configure(config):
     config.addinivalue_line(

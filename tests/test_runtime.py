@@ -176,7 +176,10 @@ print("RANK", os.environ.get("RANK", "0"), "FINAL", float(loss))
 assert float(loss) < 0.05
 sess.close()
 """)
+    # hide the GPUs so that both ranks really run on CPU: the coordinator
+    # gives rank 1 LOCAL_RANK=1, a device that a one-GPU machine lacks
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     r = subprocess.run([sys.executable, str(script)], capture_output=True,
-                       text=True, timeout=240)
+                       text=True, timeout=240, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "FINAL" in r.stdout
