@@ -12,7 +12,9 @@ class ConvBN(nn.Module):
         self.conv = nn.Conv2d(in_ch, out_ch, bias=False, **conv_kw)
         if fused:
             from autodist_amd.ops.fused_bn import FusedBatchNorm2d
-            self.bn = FusedBatchNorm2d(out_ch, relu=True)
+            # same eps as the unfused cell: fused=True swaps kernels, not
+            # the model
+            self.bn = FusedBatchNorm2d(out_ch, eps=1e-3, relu=True)
             self._act = None
         else:
             self.bn = nn.BatchNorm2d(out_ch, eps=1e-3)

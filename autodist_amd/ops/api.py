@@ -70,11 +70,25 @@ def has_fused(cls_name: str) -> bool:
     return cls_name in _FUSED_CLASSES
 
 
+def fused_supported(cls_name: str, hyper: dict) -> bool:
+    """Pure predicate: do the fused kernels implement this optimizer class
+    WITH these hyper-parameters? The Adam/AdamW kernel keeps no running
+    maximum of exp_avg_sq, so amsgrad=True goes to the torch path (which
+    implements it and keeps `max_exp_avg_sq` in the state)."""
+    if cls_name not in _FUSED_CLASSES:
+        return False
+    if cls_name in ("Adam", "AdamW") and hyper.get("amsgrad", False):
+        return False
+    return True
+
+
 def fused_apply(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
                 state: dict, hyper: dict) -> bool:
     """One-kernel optimizer update over flat bucket buffers. Returns False
-    when this optimizer class has no fused kernel (caller falls back to the
-    torch implementation)."""
+    when this optimizer class, or this combination of its flags, has no
+    fused kernel (caller falls back to the torch implementation)."""
+    if not fused_supported(cls_name, hyper):
+        return False
     if not (param.is_cuda and has_gpu_ops()):
         return False
     e = ext()
@@ -100,11 +114,13 @@ def fused_apply(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
         bc1 = 1.0 - beta1 ** step
         sqrt_bc2 = (1.0 - beta2 ** step) ** 0.5
         wd_default = 0.01 if cls_name == "AdamW" else 0.0
+        decoupled = cls_name == "AdamW" or bool(
+            hyper.get("decoupled_weight_decay", False))
         e.fused_adam(param, grad, state["exp_avg"], state["exp_avg_sq"],
                      float(hyper["lr"]), float(beta1), float(beta2),
                      float(hyper.get("eps", 1e-8)),
                      float(hyper.get("weight_decay", wd_default)),
-                     cls_name == "AdamW", bc1, sqrt_bc2,
+                     decoupled, bc1, sqrt_bc2,
                      bool(hyper.get("maximize", False)))
         return True
     if cls_name == "Adagrad":

@@ -73,7 +73,13 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
   // ws: persistent per-module workspace [2*BN_GM_MAX + 4, C] fp32:
   //   rows [0, GM)               partial sums (per reduce block)
   //   rows [BN_GM_MAX, BN_GM_MAX+GM) partial sumsq
-  //   rows 2*BN_GM_MAX + {0,1,2,3}: save_mean, save_rstd, scale, shift
+  //   rows 2*BN_GM_MAX + {0,1}: unused (kept so the layout is unchanged)
+  //   rows 2*BN_GM_MAX + {2,3}: scale, shift
+  // Everything in ws is dead once this call's apply kernel has run, so a
+  // later call on the same module may overwrite it. save_mean / save_rstd
+  // are NOT in ws: autograd keeps them until backward, and a module called
+  // twice before backward (shared tower, micro-batches summed into one
+  // loss) would otherwise hand the first backward the second call's stats.
   auto g = bn_geom(x);
   auto fopt = weight.options().dtype(torch::kFloat32);
   torch::Tensor w6 = ws.has_value() ? *ws
@@ -83,8 +89,11 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
   float* wp = w6.data_ptr<float>();
   float* partial_sum = wp;
   float* partial_sq = wp + (long)BN_GM_MAX * g.C;
-  auto save_mean = w6[2 * BN_GM_MAX + 0];
-  auto save_rstd = w6[2 * BN_GM_MAX + 1];
+  // fresh allocation: saved for backward (one caching-allocator hit, no
+  // launch)
+  auto stats = torch::empty({2, (long)g.C}, fopt);
+  auto save_mean = stats[0];
+  auto save_rstd = stats[1];
   auto scale = w6[2 * BN_GM_MAX + 2];
   auto shift = w6[2 * BN_GM_MAX + 3];
   auto y = torch::empty_like(x);
@@ -263,12 +272,12 @@ void fused_sgd(torch::Tensor p, torch::Tensor g,
     hipLaunchKernelGGL(fused_sgd_kernel<true>, grid, block, 0, cur_stream(),
                        p.data_ptr<float>(), g.data_ptr<float>(),
                        buf->data_ptr<float>(), n, (float)lr, (float)momentum,
-                       (float)dampening, (float)weight_decay, nesterov,
+                       (float)(1.0 - dampening), (float)weight_decay, nesterov,
                        first_step, maximize);
   } else {
     hipLaunchKernelGGL(fused_sgd_kernel<false>, grid, block, 0, cur_stream(),
                        p.data_ptr<float>(), g.data_ptr<float>(), nullptr, n,
-                       (float)lr, (float)momentum, (float)dampening,
+                       (float)lr, (float)momentum, (float)(1.0 - dampening),
                        (float)weight_decay, nesterov, first_step, maximize);
   }
 }
@@ -286,7 +295,8 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
                      dim3(BLOCK_THREADS), 0, cur_stream(),
                      p.data_ptr<float>(), g.data_ptr<float>(),
                      m.data_ptr<float>(), v.data_ptr<float>(), n, (float)lr,
-                     (float)beta1, (float)beta2, (float)eps,
+                     (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                     (float)(1.0 - beta2), (float)eps,
                      (float)weight_decay, adamw, (float)bc1, (float)sqrt_bc2,
                      maximize);
 }
@@ -322,8 +332,8 @@ void fused_rmsprop(torch::Tensor p, torch::Tensor g, torch::Tensor sq,
                      dim3(BLOCK_THREADS), 0, cur_stream(),
                      p.data_ptr<float>(), g.data_ptr<float>(),
                      sq.data_ptr<float>(), gap, bufp, n, (float)lr,
-                     (float)alpha, (float)eps, (float)weight_decay,
-                     (float)momentum, maximize);
+                     (float)alpha, (float)(1.0 - alpha), (float)eps,
+                     (float)weight_decay, (float)momentum, maximize);
 }
 
 void scale_cast_bf16(torch::Tensor in, torch::Tensor out, double scale) {

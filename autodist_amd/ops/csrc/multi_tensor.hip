@@ -13,11 +13,16 @@
 // ---------------------------------------------------------------- SGD
 // d = g (+ wd*p); buf = mom*buf + (1-damp)*d (or = d on first step);
 // d = nesterov ? d + mom*buf : buf; p -= lr*d
+//
+// The complements 1-damp, 1-beta, 1-alpha of all kernels in this file are
+// formed in double on the host and passed in: 1.f - 0.999f is off by 4.7e-5
+// relative (the rounding of 0.999f, magnified 1000x by the subtraction),
+// which moved every Adam update by 2.3e-5 relative to torch.optim.
 template <bool HAS_MOMENTUM>
 __global__ void fused_sgd_kernel(float* __restrict__ p,
                                  const float* __restrict__ g,
                                  float* __restrict__ buf, long n, float lr,
-                                 float momentum, float dampening,
+                                 float momentum, float one_minus_damp,
                                  float weight_decay, int nesterov,
                                  int first_step, int maximize) {
   long stride = (long)gridDim.x * blockDim.x * 4;
@@ -38,7 +43,7 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
         float br[4] = {bv.x, bv.y, bv.z, bv.w};
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          br[k] = first_step ? d[k] : momentum * br[k] + (1.f - dampening) * d[k];
+          br[k] = first_step ? d[k] : momentum * br[k] + one_minus_damp * d[k];
           d[k] = nesterov ? d[k] + momentum * br[k] : br[k];
         }
         *reinterpret_cast<float4*>(buf + base) =
@@ -53,7 +58,7 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
         float d = maximize ? -g[i] : g[i];
         d += weight_decay * p[i];
         if (HAS_MOMENTUM) {
-          float b = first_step ? d : momentum * buf[i] + (1.f - dampening) * d;
+          float b = first_step ? d : momentum * buf[i] + one_minus_damp * d;
           buf[i] = b;
           d = nesterov ? d + momentum * b : b;
         }
@@ -71,6 +76,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
                                   const float* __restrict__ g,
                                   float* __restrict__ m, float* __restrict__ v,
                                   long n, float lr, float beta1, float beta2,
+                                  float one_minus_beta1,
+                                  float one_minus_beta2,
                                   float eps, float weight_decay, int adamw,
                                   float bc1, float sqrt_bc2, int maximize) {
   long stride = (long)gridDim.x * blockDim.x * 4;
@@ -92,8 +99,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
       for (int k = 0; k < 4; ++k) {
         if (maximize) gr[k] = -gr[k];
         if (adamw) pr[k] *= wd_mul; else gr[k] += weight_decay * pr[k];
-        mr[k] = beta1 * mr[k] + (1.f - beta1) * gr[k];
-        vr[k] = beta2 * vr[k] + (1.f - beta2) * gr[k] * gr[k];
+        mr[k] = beta1 * mr[k] + one_minus_beta1 * gr[k];
+        vr[k] = beta2 * vr[k] + one_minus_beta2 * gr[k] * gr[k];
         pr[k] -= step_size * mr[k] / (sqrtf(vr[k]) / sqrt_bc2 + eps);
       }
       *reinterpret_cast<float4*>(p + base) = make_float4(pr[0], pr[1], pr[2], pr[3]);
@@ -104,8 +111,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
         float gr = maximize ? -g[i] : g[i];
         float pr = p[i];
         if (adamw) pr *= wd_mul; else gr += weight_decay * pr;
-        float mr = beta1 * m[i] + (1.f - beta1) * gr;
-        float vr = beta2 * v[i] + (1.f - beta2) * gr * gr;
+        float mr = beta1 * m[i] + one_minus_beta1 * gr;
+        float vr = beta2 * v[i] + one_minus_beta2 * gr * gr;
         p[i] = pr - step_size * mr / (sqrtf(vr) / sqrt_bc2 + eps);
         m[i] = mr;
         v[i] = vr;
@@ -251,6 +258,7 @@ __global__ void fused_rmsprop_kernel(float* __restrict__ p,
                                      float* __restrict__ ga,   // nullable
                                      float* __restrict__ buf,  // nullable
                                      long n, float lr, float alpha,
+                                     float one_minus_alpha,
                                      float eps, float weight_decay,
                                      float momentum, int maximize) {
   long stride = (long)gridDim.x * blockDim.x;
@@ -258,11 +266,11 @@ __global__ void fused_rmsprop_kernel(float* __restrict__ p,
        i += stride) {
     float d = maximize ? -g[i] : g[i];
     d += weight_decay * p[i];
-    float s = alpha * sq[i] + (1.f - alpha) * d * d;
+    float s = alpha * sq[i] + one_minus_alpha * d * d;
     sq[i] = s;
     float denom;
     if (ga != nullptr) {
-      float a = ga[i] + (1.f - alpha) * (d - ga[i]);
+      float a = ga[i] + one_minus_alpha * (d - ga[i]);
       ga[i] = a;
       denom = sqrtf(s - a * a) + eps;
     } else {

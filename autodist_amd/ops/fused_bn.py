@@ -5,8 +5,9 @@ The hot elementwise chain of the ResNet benchmark:
     relu-mask -> bn-bwd -> dres         (backward)
 runs as hand-written gfx950 kernels (csrc/bn_ops.hip): bf16-native (no
 autocast fp32 round-trip), residual-add and ReLU folded into the normalize /
-gradient passes. On CPU (CI) the same math runs via torch ops so numerics
-tests can compare.
+gradient passes. On CPU (CI) the same math runs through torch's own
+batch-norm kernels, so numerics tests can compare and a fused=True model
+equals its unfused twin bit for bit there.
 
 `FusedBatchNorm2d` is state_dict-compatible with nn.BatchNorm2d (same
 parameter/buffer names).
@@ -29,24 +30,29 @@ class _FusedBNFunction(torch.autograd.Function):
                 x, weight, bias, running_mean, running_var, residual,
                 eps, momentum, relu, ws[0] if ws is not None else None)
         else:
+            # torch's own batch-norm kernels, so that a fused=True model is
+            # the unfused model on this path down to the last bit, however
+            # ill-conditioned the network (tests/test_fused_bn.py)
             xf = x.float()
-            dims = (0, 2, 3)
             m = xf.numel() // xf.size(1)
-            mean = xf.mean(dims)
-            var = xf.var(dims, unbiased=False)
-            save_mean = mean
-            save_rstd = (var + eps).rsqrt()
             with torch.no_grad():
-                running_mean.mul_(1 - momentum).add_(mean, alpha=momentum)
-                unbiased = var * m / max(m - 1, 1)
-                running_var.mul_(1 - momentum).add_(unbiased, alpha=momentum)
-            y = (xf - mean[None, :, None, None]) * save_rstd[None, :, None, None]
-            y = y * weight[None, :, None, None] + bias[None, :, None, None]
-            if residual is not None:
-                y = y + residual.float()
-            if relu:
-                y = torch.relu(y)
-            y = y.to(x.dtype)
+                if m > 1:
+                    y, save_mean, save_rstd = torch.native_batch_norm(
+                        xf, weight, bias, running_mean, running_var, True,
+                        momentum, eps)
+                else:
+                    # one value per channel: var = 0, and the unbiased
+                    # estimate is taken as 0 too, not 0/0
+                    y, save_mean, save_rstd = torch.native_batch_norm(
+                        xf, weight, bias, None, None, True, momentum, eps)
+                    running_mean.mul_(1 - momentum).add_(save_mean,
+                                                         alpha=momentum)
+                    running_var.mul_(1 - momentum)
+                if residual is not None:
+                    y = y + residual.float()
+                if relu:
+                    y = torch.relu(y)
+                y = y.to(x.dtype)
         ctx.save_for_backward(x, y, save_mean, save_rstd, weight)
         ctx.relu = relu
         ctx.has_res = residual is not None
@@ -68,18 +74,10 @@ class _FusedBNFunction(torch.autograd.Function):
             if relu:
                 dyf = dyf * (y > 0).float()
             dres = dyf.to(dy.dtype) if has_res else None
-            m = x.numel() // x.size(1)
-            xf = x.float()
-            xhat = (xf - save_mean[None, :, None, None]) * \
-                save_rstd[None, :, None, None]
-            dims = (0, 2, 3)
-            sum_dz = dyf.sum(dims)
-            sum_dzxh = (dyf * xhat).sum(dims)
-            dxf = (weight * save_rstd)[None, :, None, None] * (
-                dyf - sum_dz[None, :, None, None] / m
-                - xhat * sum_dzxh[None, :, None, None] / m)
+            dxf, dweight, dbias = torch.ops.aten.native_batch_norm_backward(
+                dyf, x.float(), weight, None, None, save_mean, save_rstd,
+                True, 0.0, [True, True, True])
             dx = dxf.to(x.dtype)
-            dweight, dbias = sum_dzxh, sum_dz
         return (dx, dweight, dbias, None, None, None, None, None, dres, None)
 
 
@@ -124,7 +122,11 @@ class FusedBatchNorm2d(torch.nn.Module):
             self.num_batches_tracked += 1
             if x.is_cuda and (self._ws is None
                               or self._ws[0].device != x.device):
-                # layouts match BN_GM_MAX=512 in csrc/ext.hip
+                # layouts match BN_GM_MAX=512 in csrc/ext.hip: reduce
+                # partials plus scale/shift (fwd) and k1..k3 (bwd). Only
+                # values that are dead when the call returns live here;
+                # save_mean/save_rstd come back freshly allocated, so calling
+                # this module twice before backward is safe.
                 self._ws = (
                     torch.empty(2 * 512 + 4, self.num_features,
                                 device=x.device),

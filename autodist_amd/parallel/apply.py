@@ -12,9 +12,10 @@ fused launch group per bucket); on gfx950 the hand-written HIP multi-tensor
 kernels in ops/csrc/multi_tensor.hip replace them (one kernel launch per
 bucket per step, LDS-free pure-bandwidth kernels tuned for HBM3E).
 
-Supported exactly: SGD (momentum/nesterov/dampening/weight_decay/maximize),
-Adam, AdamW, Adagrad, RMSprop. Sparse rows: sparse_apply_* variants implement
-the `SparseApply*` table (op_info.py:73-117).
+Supported exactly (every constructor flag, `maximize` included; see
+tests/test_optimizer_matrix.py): SGD, Adam, AdamW, Adagrad, RMSprop, Adamax,
+NAdam, RAdam, Adadelta, ASGD, Rprop. Sparse rows: sparse_apply_* variants
+implement the `SparseApply*` table (op_info.py:73-117).
 """
 import math
 from typing import Dict, List
@@ -79,6 +80,14 @@ def make_state(cls_name: str, param: torch.Tensor, hyper: dict) -> Dict[str, tor
     raise NotImplementedError(f"optimizer {cls_name} not supported for engine apply")
 
 
+def _maybe_negate(grads, hyper):
+    """maximize=True: torch.optim negates the gradient before anything else
+    (weight decay included) in every optimizer class."""
+    if hyper.get("maximize", False):
+        grads = torch._foreach_neg(grads)
+    return grads
+
+
 def _maybe_weight_decay(grads, params, wd):
     if wd != 0:
         grads = torch._foreach_add(grads, params, alpha=wd)
@@ -118,11 +127,12 @@ def apply_sgd(params: List[torch.Tensor], grads: List[torch.Tensor],
     torch._foreach_add_(params, grads, alpha=-lr)
 
 
-def _adam_impl(params, grads, states, hyper, decoupled_wd: bool):
+def _adam_impl(params, grads, states, hyper, decoupled_wd: bool,
+               wd_default: float = 0.0):
     lr = hyper["lr"]
     beta1, beta2 = hyper.get("betas", (0.9, 0.999))
     eps = hyper.get("eps", 1e-8)
-    wd = hyper.get("weight_decay", 0.01 if decoupled_wd else 0.0)
+    wd = hyper.get("weight_decay", wd_default)
     amsgrad = hyper.get("amsgrad", False)
     maximize = hyper.get("maximize", False)
     if maximize:
@@ -155,11 +165,14 @@ def _adam_impl(params, grads, states, hyper, decoupled_wd: bool):
 
 
 def apply_adam(params, grads, states, hyper):
-    _adam_impl(params, grads, states, hyper, decoupled_wd=False)
+    # torch.optim.Adam(decoupled_weight_decay=True) is AdamW's update
+    _adam_impl(params, grads, states, hyper,
+               decoupled_wd=bool(hyper.get("decoupled_weight_decay", False)))
 
 
 def apply_adamw(params, grads, states, hyper):
-    _adam_impl(params, grads, states, hyper, decoupled_wd=True)
+    _adam_impl(params, grads, states, hyper, decoupled_wd=True,
+               wd_default=0.01)
 
 
 def apply_adagrad(params, grads, states, hyper):
@@ -167,6 +180,7 @@ def apply_adagrad(params, grads, states, hyper):
     lr_decay = hyper.get("lr_decay", 0.0)
     eps = hyper.get("eps", 1e-10)
     wd = hyper.get("weight_decay", 0.0)
+    grads = _maybe_negate(grads, hyper)
     grads = _maybe_weight_decay(grads, params, wd)
     for st in states:
         st["step"] += 1
@@ -184,6 +198,7 @@ def apply_rmsprop(params, grads, states, hyper):
     wd = hyper.get("weight_decay", 0.0)
     momentum = hyper.get("momentum", 0.0)
     centered = hyper.get("centered", False)
+    grads = _maybe_negate(grads, hyper)
     grads = _maybe_weight_decay(grads, params, wd)
     sq = [st["square_avg"] for st in states]
     torch._foreach_mul_(sq, alpha)
@@ -211,6 +226,7 @@ def apply_adamax(params, grads, states, hyper):
     beta1, beta2 = hyper.get("betas", (0.9, 0.999))
     eps = hyper.get("eps", 1e-8)
     wd = hyper.get("weight_decay", 0.0)
+    grads = _maybe_negate(grads, hyper)
     grads = _maybe_weight_decay(grads, params, wd)
     for p, g, st in zip(params, grads, states):
         st["step"] += 1
@@ -229,6 +245,7 @@ def apply_nadam(params, grads, states, hyper):
     wd = hyper.get("weight_decay", 0.0)
     psi = hyper.get("momentum_decay", 4e-3)
     decoupled = hyper.get("decoupled_weight_decay", False)
+    grads = _maybe_negate(grads, hyper)
     if wd != 0 and decoupled:
         torch._foreach_mul_(params, 1 - lr * wd)
     elif wd != 0:
@@ -255,6 +272,7 @@ def apply_radam(params, grads, states, hyper):
     eps = hyper.get("eps", 1e-8)
     wd = hyper.get("weight_decay", 0.0)
     decoupled = hyper.get("decoupled_weight_decay", False)
+    grads = _maybe_negate(grads, hyper)
     if wd != 0 and decoupled:
         torch._foreach_mul_(params, 1 - lr * wd)
     elif wd != 0:
@@ -283,6 +301,7 @@ def apply_adadelta(params, grads, states, hyper):
     rho = hyper.get("rho", 0.9)
     eps = hyper.get("eps", 1e-6)
     wd = hyper.get("weight_decay", 0.0)
+    grads = _maybe_negate(grads, hyper)
     grads = _maybe_weight_decay(grads, params, wd)
     for p, g, st in zip(params, grads, states):
         st["step"] += 1
@@ -299,6 +318,7 @@ def apply_asgd(params, grads, states, hyper):
     alpha = hyper.get("alpha", 0.75)
     t0 = hyper.get("t0", 1e6)
     wd = hyper.get("weight_decay", 0.0)
+    grads = _maybe_negate(grads, hyper)
     grads = _maybe_weight_decay(grads, params, wd)
     for p, g, st in zip(params, grads, states):
         st["step"] += 1
@@ -318,6 +338,7 @@ def apply_asgd(params, grads, states, hyper):
 def apply_rprop(params, grads, states, hyper):
     etaminus, etaplus = hyper.get("etas", (0.5, 1.2))
     step_min, step_max = hyper.get("step_sizes", (1e-6, 50.0))
+    grads = _maybe_negate(grads, hyper)
     for p, g, st in zip(params, grads, states):
         st["step"] += 1
         sign = g.mul(st["prev"]).sign()

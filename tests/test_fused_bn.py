@@ -2,6 +2,7 @@
 kernels are checked against the same references in test_gpu_kernels.py."""
 import copy
 
+import pytest
 import torch
 
 from autodist_amd.ops.fused_bn import FusedBatchNorm2d, fused_bn_train
@@ -69,6 +70,108 @@ def test_resnet18_fused_matches_unfused_cpu():
                                   m_fused.named_parameters()):
         assert torch.allclose(p1.grad, p2.grad, atol=1e-3), \
             f"{n1}: {(p1.grad - p2.grad).abs().max()}"
+
+
+def _assert_fused_matches_unfused(make, x):
+    """fused=True must swap kernels, not the model: same forward output and
+    parameter gradients on the fallback path (tolerances of the ResNet-18
+    test above). Dropout masks are made equal by reseeding. Parameters are
+    paired by order: VGG's unfused variant has separate ReLU modules, so
+    its Sequential indices differ."""
+    torch.manual_seed(0)
+    m_ref = make(fused=False)
+    m_fused = make(fused=True)
+    p_ref, p_fused = list(m_ref.parameters()), list(m_fused.parameters())
+    assert [p.shape for p in p_ref] == [p.shape for p in p_fused]
+    with torch.no_grad():
+        for a, b in zip(p_ref, p_fused):
+            b.copy_(a)
+    bn_ref = [m for m in m_ref.modules()
+              if isinstance(m, torch.nn.BatchNorm2d)]
+    bn_fused = [m for m in m_fused.modules()
+                if isinstance(m, FusedBatchNorm2d)]
+    assert len(bn_ref) == len(bn_fused) > 0
+    for a, b in zip(bn_ref, bn_fused):
+        assert (a.eps, a.momentum) == (b.eps, b.momentum)
+    torch.manual_seed(1)
+    y_ref = m_ref(x)
+    torch.manual_seed(1)
+    y_fused = m_fused(x)
+    assert torch.allclose(y_ref, y_fused, atol=1e-4), \
+        (y_ref - y_fused).abs().max()
+    y_ref.square().mean().backward()
+    y_fused.square().mean().backward()
+    names = [n for n, _ in m_ref.named_parameters()]
+    for n, a, b in zip(names, p_ref, p_fused):
+        assert torch.allclose(a.grad, b.grad, atol=1e-3), \
+            f"{n}: {(a.grad - b.grad).abs().max()}"
+    for a, b in zip(bn_ref, bn_fused):
+        assert torch.allclose(a.running_var, b.running_var, atol=1e-4,
+                              rtol=1e-4)
+
+
+def test_inception_v3_fused_matches_unfused_cpu():
+    """Whole model, batch 2, 75x75 (the smallest input the model accepts),
+    fp32, tolerances of the ResNet-18 test.
+
+    At this size the last two cells run at 1x1: their BatchNorms normalise
+    over TWO values per channel, xhat is a smoothed sign function with slope
+    1/sqrt(eps) = 32 at zero, and a rounding difference grows by that factor
+    through every BN layer in series (torch's own fp32 model is 2e-2 in the
+    output and 4e2 in the gradients away from its float64 copy). The
+    tolerances hold only because the fallback path of fused_bn.py runs
+    torch's own batch-norm kernels, which makes the two variants agree bit
+    for bit. With eps=1e-5 in the fused cells against 1e-3 it fails."""
+    from autodist_amd.models.inception import inception_v3
+    _assert_fused_matches_unfused(
+        lambda fused: inception_v3(num_classes=10, fused=fused),
+        torch.randn(2, 3, 75, 75, generator=torch.Generator().manual_seed(3)))
+
+
+def test_inception_cells_fused_match_unfused_cpu():
+    """Every top-level cell of Inception v3, fused vs unfused, fed the SAME
+    input (the unfused model's activation), so one cell's rounding is not
+    amplified by the next: forward output, input gradient and parameter
+    gradients at the ResNet-18 tolerances. 107x107 is the smallest input
+    that leaves more than two values per channel in the last cells. With
+    the fused cells at eps=1e-5 against 1e-3 this fails at the first cell,
+    and it names the cell."""
+    from autodist_amd.models.inception import inception_v3
+    torch.manual_seed(0)
+    m_ref = inception_v3(num_classes=10, fused=False)
+    m_fused = inception_v3(num_classes=10, fused=True)
+    with torch.no_grad():
+        for a, b in zip(m_ref.parameters(), m_fused.parameters()):
+            b.copy_(a)
+    h = torch.randn(2, 3, 107, 107,
+                    generator=torch.Generator().manual_seed(3))
+    cells_ref = list(m_ref.stem) + list(m_ref.mixed)
+    cells_fused = list(m_fused.stem) + list(m_fused.mixed)
+    for i, (c_ref, c_fused) in enumerate(zip(cells_ref, cells_fused)):
+        h1 = h.detach().clone().requires_grad_(True)
+        h2 = h.detach().clone().requires_grad_(True)
+        y1, y2 = c_ref(h1), c_fused(h2)
+        assert torch.allclose(y1, y2, atol=1e-4), \
+            f"cell {i}: {(y1 - y2).abs().max()}"
+        g = torch.randn(y1.shape, generator=torch.Generator().manual_seed(i))
+        g = g / g.numel() ** 0.5
+        y1.backward(g)
+        y2.backward(g)
+        assert torch.allclose(h1.grad, h2.grad, atol=1e-3), \
+            f"cell {i} dx: {(h1.grad - h2.grad).abs().max()}"
+        for (n, a), b in zip(c_ref.named_parameters(),
+                             c_fused.parameters()):
+            assert torch.allclose(a.grad, b.grad, atol=1e-3), \
+                f"cell {i} {n}: {(a.grad - b.grad).abs().max()}"
+        h = y1.detach()
+
+
+def test_vgg16_bn_fused_matches_unfused_cpu():
+    from autodist_amd.models.vgg import vgg16
+    # 32x32: five 2x2 max-pools leave 1x1
+    _assert_fused_matches_unfused(
+        lambda fused: vgg16(num_classes=10, batch_norm=True, fused=fused),
+        torch.randn(2, 3, 32, 32, generator=torch.Generator().manual_seed(4)))
 
 
 def test_fused_bn_eval_mode():

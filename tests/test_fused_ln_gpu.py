@@ -1,4 +1,6 @@
 """Fused bf16 LayerNorm(+residual) kernels vs fp32 torch reference."""
+import math
+
 import pytest
 import torch
 
@@ -128,3 +130,168 @@ def test_fused_ce_vs_torch():
     assert abs(loss.item() - ref.item()) < 2e-3 * abs(ref.item()) + 1e-3
     err = (lg.grad.float() - lr.grad).abs().max().item()
     assert err < 5e-5, f"dlogits err {err}"  # grads are O(1/N)
+
+
+# ---------------------------------------------------------------------------
+# Geometry and edge cases. Error model, as in tests/test_bn_geometry_gpu.py:
+#   * integer-valued dy / inputs make column sums exact in fp32 -> torch.equal
+#   * bf16-stored elementwise outputs: 2^-7 * B + 1e-6, B = sum of |terms|
+#   * fp32 reductions: L * 2^-24 * sum|terms|, L = sequential adds in the
+#     kernel, plus what that error does to values derived from the reduction
+# References are float64 on the same bf16 inputs; the backward reference
+# takes the kernel's own u / mean / rstd, which are inputs of ln_bwd.
+U24 = 2.0 ** -24
+BF16 = 2.0 ** -7
+
+
+def _within(name, got, ref, tol):
+    err = (got.double() - ref).abs()
+    tol = tol.expand_as(err)
+    bad = ~(err <= tol)
+    assert not bad.any(), (
+        f"{name}: {int(bad.sum())} of {bad.numel()} outside the bound, "
+        f"max err/tol {(err / tol).max().item():.3f}, "
+        f"max err {err.max().item():.3e}")
+
+
+def _ln_chain(H):
+    # per thread: ceil(H/2 / 256) pair-iterations of 2 adds; then 4 DPP
+    # rotate-adds, 2 cross-group shuffles, 3 adds over the 4 waves; + the
+    # division and the roundings inside a term
+    return 2 * -(-(H // 2) // 256) + 4 + 2 + 3 + 4
+
+
+@pytest.mark.parametrize("with_res", [True, False], ids=["res", "nores"])
+@pytest.mark.parametrize("N,H", [
+    (1, 2),        # one pair: one live thread per row
+    (300, 100),    # two ln_bwd_gb row-chunks (blockIdx.y = 1), ragged 2nd
+    (513, 514),    # three chunks, last one a single row; ragged pair-iter
+    (257, 4094),   # ragged LAST pair-iteration of 8
+    (5, 4096),     # H = 256 * LN_MAX_PER_THREAD, the register-array limit
+])
+def test_ln_geometry(ext, N, H, with_res):
+    eps = 1e-5
+    g = torch.Generator(device="cuda").manual_seed(N * 10007 + H)
+    rnd = lambda *s: torch.randn(*s, generator=g, device="cuda")  # noqa: E731
+    x = rnd(N, H).bfloat16()
+    res = rnd(N, H).bfloat16() if with_res else None
+    gamma = rnd(H) * 0.5 + 1.0
+    beta = rnd(H) * 0.1
+    dy = torch.randint(-4, 5, (N, H), generator=g, device="cuda").bfloat16()
+    y, u, mean, rstd = ext.ln_fwd(x, res, gamma, beta, eps)
+    L = _ln_chain(H)
+
+    # ---- forward: y is computed from the UNROUNDED fp32 sum x + res
+    ud = x.double() + (res.double() if with_res else 0.0)
+    if with_res:
+        assert torch.equal(u, (x.float() + res.float()).bfloat16())
+    else:
+        assert u.data_ptr() == x.data_ptr() and torch.equal(u, x)
+    m_ref = ud.mean(1)
+    ex2 = (ud * ud).mean(1)
+    var = (ex2 - m_ref * m_ref).clamp_min(0)
+    r_ref = (var + eps).rsqrt()
+    tol_m = L * U24 * ud.abs().mean(1) + 1e-30
+    tol_v = L * U24 * (ex2 + 2 * m_ref.abs() * ud.abs().mean(1)) + 1e-30
+    tol_r = 0.5 * r_ref ** 3 * tol_v + 4 * U24 * r_ref
+    _within("mean", mean, m_ref, tol_m)
+    _within("rstd", rstd, r_ref, tol_r)
+    gd, bd = gamma.double(), beta.double()
+    cen = ud - m_ref[:, None]
+    y_ref = cen * r_ref[:, None] * gd + bd
+    B = (ud.abs() + m_ref.abs()[:, None]) * r_ref[:, None] * gd.abs() \
+        + bd.abs()
+    _within("y", y, y_ref, BF16 * B + 1e-6
+            + (r_ref * tol_m)[:, None] * gd.abs()
+            + cen.abs() * gd.abs() * tol_r[:, None])
+
+    # ---- backward, from the kernel's own u / mean / rstd
+    dx, dgamma, dbeta = ext.ln_bwd(dy, u, gamma, mean, rstd)
+    dyd, md, rd = dy.double(), mean.double(), rstd.double()
+    xh = (u.double() - md[:, None]) * rd[:, None]
+    # exact: integers, |column sum| <= 4 * 513 < 2^24, also across chunks
+    assert torch.equal(dbeta, dyd.sum(0).float()), \
+        (dbeta.double() - dyd.sum(0)).abs().max()
+    # ln_bwd_gb: 64 sequential adds per row-lane of a 256-row chunk, 3 to
+    # combine the lanes, then the chunks; + the roundings inside a term
+    Lg = 64 + 3 + -(-N // 256) + 4
+    _within("dgamma", dgamma, (dyd * xh).sum(0),
+            Lg * U24 * (dyd * xh).abs().sum(0) + 1e-30)
+    gg = dyd * gd
+    c1, c2 = gg.mean(1, keepdim=True), (gg * xh).mean(1, keepdim=True)
+    t1 = L * U24 * gg.abs().mean(1, keepdim=True)
+    t2 = L * U24 * (gg * xh).abs().mean(1, keepdim=True)
+    dx_ref = rd[:, None] * (gg - c1 - xh * c2)
+    Bx = rd[:, None] * (gg.abs() + c1.abs() + (xh * c2).abs())
+    _within("dx", dx, dx_ref,
+            BF16 * Bx + 1e-6 + rd[:, None] * (t1 + xh.abs() * t2))
+
+
+def test_ln_constant_row(ext):
+    """A constant row has var = 0: with eps = 1e-5 it must come out finite
+    and equal to beta (xhat = 0). 3.0 * H is exact in fp32, so mean is."""
+    N, H = 3, 100
+    x = torch.randn(N, H, device="cuda").bfloat16()
+    x[1] = 3.0
+    gamma = torch.rand(H, device="cuda") + 0.5
+    beta = torch.randn(H, device="cuda")
+    y, u, mean, rstd = ext.ln_fwd(x, None, gamma, beta, 1e-5)
+    assert torch.isfinite(y.float()).all() and torch.isfinite(rstd).all()
+    assert mean[1].item() == 3.0
+    _within("y[const]", y[1], beta.double(),
+            BF16 * beta.double().abs() + 1e-6)
+    dy = torch.randint(-4, 5, (N, H), device="cuda").bfloat16()
+    dx, dgamma, dbeta = ext.ln_bwd(dy, u, gamma, mean, rstd)
+    assert torch.isfinite(dx.float()).all()
+    assert torch.isfinite(dgamma).all()
+
+
+@pytest.mark.parametrize("N,H", [
+    (1, 64),        # one row, one column block
+    (513, 100),     # ragged column block (H % 64 != 0), ragged 2nd chunk
+    (131079, 64),   # nchunks > 256: the re-chunk branch, ragged last chunk
+])
+def test_col_sum_exact(ext, N, H):
+    g = torch.Generator(device="cuda").manual_seed(N + H)
+    x = torch.randint(-4, 5, (N, H), generator=g, device="cuda")
+    got = ext.col_sum(x.bfloat16())
+    # |sum| <= 4 * 131079 < 2^24: every fp32 partial sum is exact
+    assert got.shape == (H,)
+    assert torch.equal(got.double(), x.sum(0).double()), \
+        (got.double() - x.sum(0).double()).abs().max()
+
+
+@pytest.mark.parametrize("V", [1, 2, 255, 256, 257, 1000])
+def test_fused_ce_edges(ext, V):
+    """V < 256 leaves idle threads in the tree combine, V % 256 != 0 a
+    ragged last stride; large logits, an all-equal row, -inf entries,
+    targets at both ends, and a non-uniform upstream gradient."""
+    N = 7
+    g = torch.Generator(device="cuda").manual_seed(V)
+    logits = torch.randn(N, V, generator=g, device="cuda")
+    logits = (logits * (80.0 / logits.abs().max())).bfloat16()
+    logits[0] = 60.0                       # all equal: loss = ln V
+    targets = torch.randint(0, V, (N,), generator=g, device="cuda")
+    targets[2], targets[3] = 0, V - 1
+    if V > 1:                              # -inf entries, finite target
+        logits[1, 1::2] = float("-inf")
+        targets[1] = 0
+    dloss = torch.tensor([1.0, 0.5, 0.0, -2.0, 3.0, 1.0 / 7, 0.25],
+                         device="cuda")
+    loss, m, l2s = ext.ce_fwd(logits, targets)
+    dlog = ext.ce_bwd(logits, targets, m, l2s, dloss)
+
+    ld = logits.double()
+    lsm = torch.log_softmax(ld, dim=1)
+    loss_ref = -lsm.gather(1, targets[:, None])[:, 0]
+    assert abs(loss_ref[0].item() - math.log(V)) < 1e-12
+    row_max = ld.max(1).values.abs()
+    _within("loss", loss, loss_ref,
+            2.0 ** -20 * (row_max * math.log2(math.e)).clamp_min(1.0))
+    d_ref = lsm.exp()
+    d_ref[torch.arange(N), targets] -= 1.0
+    d_ref = d_ref * dloss.double()[:, None]
+    assert torch.isfinite(dlog.float()).all()
+    _within("dlogits", dlog, d_ref,
+            BF16 * d_ref.abs() + 1e-4 * dloss.double().abs()[:, None])
+    assert torch.equal(dlog[2], torch.zeros_like(dlog[2]))  # weight 0

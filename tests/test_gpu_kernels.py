@@ -1,7 +1,10 @@
 """Numerics tests for the gfx950 HIP kernels vs plain PyTorch fp32 references.
 
 Every kernel in ops/csrc/*.hip has a test here (run with `-m gpu` on an
-MI355X box)."""
+MI355X box), at one or two shapes in its simplest launch geometry. The other
+branches of the launch maths and the optimizer flags are covered in
+test_bn_geometry_gpu.py, test_fused_ln_gpu.py and
+test_optimizer_matrix_gpu.py."""
 import pytest
 import torch
 
