@@ -48,6 +48,7 @@ class ENV(enum.Enum):
     AUTODIST_DEBUG_REMOTE = ((lambda v: v == "True" or v == "1"),)  # dry-run remote exec
     AUTODIST_RANK = ((lambda v: int(v) if v else None),)            # explicit rank override
     AUTODIST_RESOURCE_SPEC = ((lambda v: v or ""),)                 # path to resource spec yaml
+    AUTODIST_SPARSE_PS_ROUTING = ((lambda v: v or "replicated"),)   # PS builders' default sparse_routing ("replicated" | "owner")
 
     @property
     def val(self):

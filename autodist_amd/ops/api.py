@@ -145,6 +145,69 @@ def fused_apply(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
     return False
 
 
+_SPARSE_FUSED_IDS = {"SGD": 0, "Adagrad": 1, "Adam": 2, "AdamW": 2,
+                     "SparseAdam": 2}
+
+
+def fused_sparse_apply(cls_name: str, param: torch.Tensor,
+                       rows: torch.Tensor, row_grads: torch.Tensor,
+                       state: dict, hyper: dict, row_base: int = 0,
+                       new_rows: torch.Tensor = None) -> bool:
+    """One-kernel row-wise optimizer update of UNIQUE rows (the sparse
+    counterpart of fused_apply). `rows` holds global row ids; `param` (and
+    the state tensors) hold rows [row_base, row_base + len(param)) — ids
+    outside that range are skipped. With `new_rows` [n, D] the updated
+    parameter rows are also written there in the same pass.
+
+    Returns False when this optimizer class / flag combination / tensor
+    layout has no kernel (caller falls back to the torch implementation)."""
+    opt_id = _SPARSE_FUSED_IDS.get(cls_name)
+    if opt_id is None:
+        return False
+    if cls_name == "SGD" and (hyper.get("momentum", 0)
+                              or hyper.get("weight_decay", 0)):
+        return False  # the torch path raises torch.optim's error for these
+    # hot path (every sparse variable, every step): a GPU tensor implies a
+    # GPU, so ask only whether the extension is loaded
+    e = _load() if param.is_cuda else None
+    if e is None:
+        return False
+    tensors = [param, row_grads]
+    if opt_id == 1:
+        tensors.append(state["sum"])
+    elif opt_id == 2:
+        tensors += [state["exp_avg"], state["exp_avg_sq"]]
+    if new_rows is not None:
+        tensors.append(new_rows)
+    if not all(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+               for t in tensors):
+        return False
+    if not (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 1
+            and rows.is_contiguous()):
+        return False
+    lr = float(hyper["lr"])
+    if opt_id == 0:
+        e.sparse_apply_rows(0, param, rows, row_grads, None, None, new_rows,
+                            int(row_base), lr, 0.0, 0.0, 0.0, 1.0, 1.0)
+        return True
+    state["step"] += 1
+    step = float(state["step"])
+    if opt_id == 1:
+        clr = lr / (1.0 + (step - 1.0) * float(hyper.get("lr_decay", 0.0)))
+        e.sparse_apply_rows(1, param, rows, row_grads, state["sum"], None,
+                            new_rows, int(row_base), clr, 0.0, 0.0,
+                            float(hyper.get("eps", 1e-10)), 1.0, 1.0)
+        return True
+    beta1, beta2 = hyper.get("betas", (0.9, 0.999))
+    bc1 = 1.0 - beta1 ** step
+    sqrt_bc2 = (1.0 - beta2 ** step) ** 0.5
+    e.sparse_apply_rows(2, param, rows, row_grads, state["exp_avg"],
+                        state["exp_avg_sq"], new_rows, int(row_base), lr,
+                        float(beta1), float(beta2),
+                        float(hyper.get("eps", 1e-8)), bc1, sqrt_bc2)
+    return True
+
+
 def scale_cast_bf16(inp: torch.Tensor, out: torch.Tensor, scale: float):
     if inp.is_cuda and has_gpu_ops():
         ext().scale_cast_bf16(inp, out, float(scale))

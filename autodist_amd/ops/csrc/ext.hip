@@ -420,6 +420,103 @@ torch::Tensor gather_rows(torch::Tensor src, torch::Tensor idx) {
   return out;
 }
 
+// Row-wise optimizer apply for unique rows (see multi_tensor.hip). opt:
+// 0 = SGD, 1 = Adagrad (lr is the host-decayed clr), 2 = Adam/SparseAdam.
+template <int OPT>
+static void launch_sparse_apply(bool vec4, dim3 grid, float* p,
+                                const int64_t* rows, const float* g,
+                                float* s1, float* s2, float* out, long n,
+                                long R, long D, long row_base, int log2_group,
+                                SparseHyper h) {
+  if (vec4) {
+    hipLaunchKernelGGL((sparse_apply_rows_kernel<OPT, 4>), grid,
+                       dim3(BLOCK_THREADS), 0, cur_stream(), p, rows, g, s1,
+                       s2, out, n, R, D, row_base, log2_group, h);
+  } else {
+    hipLaunchKernelGGL((sparse_apply_rows_kernel<OPT, 1>), grid,
+                       dim3(BLOCK_THREADS), 0, cur_stream(), p, rows, g, s1,
+                       s2, out, n, R, D, row_base, log2_group, h);
+  }
+}
+
+static bool aligned16(const void* ptr) {
+  return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0;
+}
+
+void sparse_apply_rows(int64_t opt, torch::Tensor param, torch::Tensor rows,
+                       torch::Tensor row_grads,
+                       c10::optional<torch::Tensor> state1,
+                       c10::optional<torch::Tensor> state2,
+                       c10::optional<torch::Tensor> new_rows, int64_t row_base,
+                       double lr, double beta1, double beta2, double eps,
+                       double bc1, double sqrt_bc2) {
+  TORCH_CHECK(opt >= SPARSE_SGD && opt <= SPARSE_ADAM, "unknown optimizer id");
+  check_f32_flat(param, "param");
+  check_f32_flat(row_grads, "row_grads");
+  TORCH_CHECK(rows.is_cuda() && rows.is_contiguous() && rows.dim() == 1 &&
+              rows.scalar_type() == torch::kInt64,
+              "rows must be a contiguous 1-D int64 GPU tensor");
+  TORCH_CHECK(param.dim() >= 1, "param must have a row dimension");
+  TORCH_CHECK(row_base >= 0, "row_base must be non-negative");
+  long n = rows.numel();
+  long R = param.size(0);
+  long D = R > 0 ? param.numel() / R : 0;
+  TORCH_CHECK(R == 0 || row_grads.numel() == n * D,
+              "row_grads must be [n, D]");
+  bool has1 = state1.has_value() && state1->defined();
+  bool has2 = state2.has_value() && state2->defined();
+  TORCH_CHECK(has1 == (opt != SPARSE_SGD) && has2 == (opt == SPARSE_ADAM),
+              "state tensors do not match the optimizer");
+  float* s1 = nullptr;
+  float* s2 = nullptr;
+  if (has1) {
+    check_f32_flat(*state1, "state1");
+    TORCH_CHECK(state1->numel() == param.numel(), "state1 must be [R, D]");
+    s1 = state1->data_ptr<float>();
+  }
+  if (has2) {
+    check_f32_flat(*state2, "state2");
+    TORCH_CHECK(state2->numel() == param.numel(), "state2 must be [R, D]");
+    s2 = state2->data_ptr<float>();
+  }
+  float* out = nullptr;
+  if (new_rows.has_value() && new_rows->defined()) {
+    check_f32_flat(*new_rows, "new_rows");
+    TORCH_CHECK(new_rows->numel() == row_grads.numel(),
+                "new_rows must be [n, D]");
+    out = new_rows->data_ptr<float>();
+  }
+  if (n == 0 || R == 0 || D == 0) return;  // nothing to launch
+  float* p = param.data_ptr<float>();
+  const float* g = row_grads.data_ptr<float>();
+  // float4 path needs every row start 16-byte aligned: D % 4 == 0 and
+  // aligned bases (a narrow(0, ..) shard view keeps alignment when D % 4 == 0)
+  bool vec4 = D % 4 == 0 && aligned16(p) && aligned16(g) &&
+              (s1 == nullptr || aligned16(s1)) &&
+              (s2 == nullptr || aligned16(s2)) &&
+              (out == nullptr || aligned16(out));
+  long chunks = vec4 ? D / 4 : D;
+  int log2_group = 0;
+  while (log2_group < 6 && (1L << log2_group) < chunks) ++log2_group;
+  long rows_per_block = BLOCK_THREADS >> log2_group;
+  long blocks = (n + rows_per_block - 1) / rows_per_block;
+  if (blocks > 65535L * 8) blocks = 65535L * 8;
+  dim3 grid((unsigned)blocks);
+  SparseHyper h{(float)lr, (float)beta1, (float)beta2, (float)(1.0 - beta1),
+                (float)(1.0 - beta2), (float)eps, (float)bc1, (float)sqrt_bc2};
+  const int64_t* rp = rows.data_ptr<int64_t>();
+  if (opt == SPARSE_SGD) {
+    launch_sparse_apply<SPARSE_SGD>(vec4, grid, p, rp, g, s1, s2, out, n, R,
+                                    D, row_base, log2_group, h);
+  } else if (opt == SPARSE_ADAGRAD) {
+    launch_sparse_apply<SPARSE_ADAGRAD>(vec4, grid, p, rp, g, s1, s2, out, n,
+                                        R, D, row_base, log2_group, h);
+  } else {
+    launch_sparse_apply<SPARSE_ADAM>(vec4, grid, p, rp, g, s1, s2, out, n, R,
+                                     D, row_base, log2_group, h);
+  }
+}
+
 // ------------------------------------------------------------- PowerSGD
 torch::Tensor psgd_mq(torch::Tensor M2d, torch::Tensor Qp) {
   long n = M2d.size(0), s = M2d.size(1);
@@ -751,6 +848,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dedup-sum row-sparse gradient");
   m.def("scatter_add_rows", &scatter_add_rows, "rowwise scatter-add");
   m.def("gather_rows", &gather_rows, "rowwise gather");
+  m.def("sparse_apply_rows", &sparse_apply_rows,
+        "fused row-wise SGD/Adagrad/Adam update of unique rows (gfx950)");
   m.def("bn_fwd_train", &bn_fwd_train,
         "fused NHWC batchnorm fwd (+add+relu), returns y/save_mean/save_rstd");
   m.def("bn_bwd", &bn_bwd,

@@ -285,3 +285,106 @@ __global__ void fused_rmsprop_kernel(float* __restrict__ p,
     }
   }
 }
+
+// ------------------------------------------ row-wise (sparse) optimizer apply
+// The SparseApply* table (reference op_info.py:73-117) for UNIQUE rows: for
+// each i, r = rows[i] - row_base; rows r of param (and of the state tensors)
+// take one optimizer step with gradient row_grads[i]. rows are unique (the
+// caller coalesces first), so every (row, column) element has exactly one
+// writer and no atomics are needed. An r outside [0, R) is skipped and never
+// dereferenced — the shard owner only holds rows [row_base, row_base + R).
+// When `out` is given, the updated parameter row is also written to out[i]
+// in the same pass (the owner's pull payload; no separate gather).
+//
+//   SGD:     p -= lr * g
+//   Adagrad: s += g^2 ; p -= clr * (g / (sqrt(s) + eps))   (clr host-computed)
+//   Adam:    m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g^2 ;
+//            p -= lr * (m / bc1 / (sqrt(v)/sqrt(bc2) + eps))
+//            (SparseAdam semantics: moments move on touched rows only)
+//
+// Lane mapping: a power-of-two lane group (1..64 lanes) owns one row and walks
+// its D/VEC chunks; a 256-thread block therefore covers 256/group rows, so a
+// narrow row (D=8: two float4 chunks) keeps every lane of the wave busy
+// instead of leaving 62 of 64 idle. Grid-stride over row groups.
+enum { SPARSE_SGD = 0, SPARSE_ADAGRAD = 1, SPARSE_ADAM = 2 };
+
+struct SparseHyper {
+  float lr;  // clr for Adagrad
+  float beta1, beta2, one_minus_beta1, one_minus_beta2;
+  float eps, bc1, sqrt_bc2;
+};
+
+template <int OPT>
+__device__ __forceinline__ void sparse_update_elem(float& p, float g,
+                                                   float& s1, float& s2,
+                                                   const SparseHyper& h) {
+  if (OPT == SPARSE_SGD) {
+    p -= h.lr * g;
+  } else if (OPT == SPARSE_ADAGRAD) {
+    s1 += g * g;
+    p -= h.lr * (g / (sqrtf(s1) + h.eps));
+  } else {
+    s1 = h.beta1 * s1 + h.one_minus_beta1 * g;
+    s2 = h.beta2 * s2 + h.one_minus_beta2 * g * g;
+    p -= h.lr * (s1 / h.bc1 / (sqrtf(s2) / h.sqrt_bc2 + h.eps));
+  }
+}
+
+template <int OPT, int VEC>
+__global__ void sparse_apply_rows_kernel(float* __restrict__ p,
+                                         const int64_t* __restrict__ rows,
+                                         const float* __restrict__ g,
+                                         float* __restrict__ s1,   // null: SGD
+                                         float* __restrict__ s2,   // Adam only
+                                         float* __restrict__ out,  // nullable
+                                         long n, long R, long D, long row_base,
+                                         int log2_group, SparseHyper h) {
+  const int group = 1 << log2_group;
+  const int rows_per_block = BLOCK_THREADS >> log2_group;
+  const int lane = threadIdx.x & (group - 1);
+  const long chunks = D / VEC;
+  const long stride = (long)gridDim.x * rows_per_block;
+  for (long i = (long)blockIdx.x * rows_per_block + (threadIdx.x >> log2_group);
+       i < n; i += stride) {
+    const long id = rows[i];
+    if (id < row_base || id - row_base >= R) continue;  // not this shard's row
+    const long pbase = (id - row_base) * D;
+    const long gbase = i * D;
+    for (long c = lane; c < chunks; c += group) {
+      const long po = pbase + c * VEC;
+      const long go = gbase + c * VEC;
+      if (VEC == 4) {
+        float4 pv = *reinterpret_cast<float4*>(p + po);
+        float4 gv = *reinterpret_cast<const float4*>(g + go);
+        float4 av = make_float4(0.f, 0.f, 0.f, 0.f), bv = av;
+        if (OPT != SPARSE_SGD) av = *reinterpret_cast<float4*>(s1 + po);
+        if (OPT == SPARSE_ADAM) bv = *reinterpret_cast<float4*>(s2 + po);
+        float pr[4] = {pv.x, pv.y, pv.z, pv.w};
+        float gr[4] = {gv.x, gv.y, gv.z, gv.w};
+        float ar[4] = {av.x, av.y, av.z, av.w};
+        float br[4] = {bv.x, bv.y, bv.z, bv.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          sparse_update_elem<OPT>(pr[k], gr[k], ar[k], br[k], h);
+        pv = make_float4(pr[0], pr[1], pr[2], pr[3]);
+        *reinterpret_cast<float4*>(p + po) = pv;
+        if (OPT != SPARSE_SGD)
+          *reinterpret_cast<float4*>(s1 + po) =
+              make_float4(ar[0], ar[1], ar[2], ar[3]);
+        if (OPT == SPARSE_ADAM)
+          *reinterpret_cast<float4*>(s2 + po) =
+              make_float4(br[0], br[1], br[2], br[3]);
+        if (out != nullptr) *reinterpret_cast<float4*>(out + go) = pv;
+      } else {
+        float pr = p[po], a = 0.f, b = 0.f;
+        if (OPT != SPARSE_SGD) a = s1[po];
+        if (OPT == SPARSE_ADAM) b = s2[po];
+        sparse_update_elem<OPT>(pr, g[go], a, b, h);
+        p[po] = pr;
+        if (OPT != SPARSE_SGD) s1[po] = a;
+        if (OPT == SPARSE_ADAM) s2[po] = b;
+        if (out != nullptr) out[go] = pr;
+      }
+    }
+  }
+}

@@ -399,10 +399,56 @@ def apply_flat(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
 # -- sparse (row-wise) applies: the SparseApply* table ----------------------
 
 def apply_sparse_rows(cls_name: str, param: torch.Tensor, rows: torch.Tensor,
-                      row_grads: torch.Tensor, state: dict, hyper: dict):
+                      row_grads: torch.Tensor, state: dict, hyper: dict,
+                      row_base: int = 0, new_rows: torch.Tensor = None):
     """Row-sparse update: only `rows` of param are touched (embedding grads).
     Matches torch.optim sparse semantics (SGD/Adagrad support sparse grads;
-    sparse Adam follows torch.optim.SparseAdam)."""
+    sparse Adam follows torch.optim.SparseAdam).
+
+    `rows` are UNIQUE global row ids; `param` and the state tensors hold rows
+    [row_base, row_base + len(param)) (a PS shard owner passes its shard view
+    and shard-local state). With `new_rows` [n, D], the updated parameter
+    rows are also written to new_rows[i] (the owner's pull payload).
+
+    fp32 contiguous GPU tensors go through ONE hand-written gfx950 HIP kernel
+    (ops/csrc/multi_tensor.hip); the torch composite below is the CPU path
+    and the fallback for everything the kernel does not cover."""
+    if param.is_cuda:
+        from autodist_amd.ops import api as ops_api
+        if ops_api.fused_sparse_apply(cls_name, param, rows, row_grads,
+                                      state, hyper, row_base=row_base,
+                                      new_rows=new_rows):
+            return
+    apply_sparse_rows_torch(cls_name, param, rows, row_grads, state, hyper,
+                            row_base=row_base, new_rows=new_rows)
+
+
+def apply_sparse_rows_torch(cls_name: str, param: torch.Tensor,
+                            rows: torch.Tensor, row_grads: torch.Tensor,
+                            state: dict, hyper: dict, row_base: int = 0,
+                            new_rows: torch.Tensor = None):
+    """The torch composite behind apply_sparse_rows (same contract)."""
+    if row_base or new_rows is not None:
+        # shard-local coordinates; ids outside the shard are skipped, the
+        # optimizer's step counter still advances (a global step)
+        local = rows - row_base
+        keep = (local >= 0) & (local < param.shape[0])
+        if bool(keep.all()):
+            keep = None
+        else:
+            local, row_grads = local[keep], row_grads[keep]
+        _sparse_rows_update(cls_name, param, local, row_grads, state, hyper)
+        if new_rows is not None:
+            fresh = param.index_select(0, local)
+            if keep is None:
+                new_rows.copy_(fresh)
+            else:
+                new_rows[keep] = fresh
+        return
+    _sparse_rows_update(cls_name, param, rows, row_grads, state, hyper)
+
+
+def _sparse_rows_update(cls_name, param, rows, row_grads, state, hyper):
     if cls_name == "SGD":
         # torch SGD rejects sparse grads with momentum/weight_decay; match it
         if hyper.get("momentum", 0) or hyper.get("weight_decay", 0):

@@ -4,7 +4,9 @@ Reference context: sparse gradients synchronize via two collective_ops
 all_gather calls on indices/values (all_reduce_synchronizer.py:132-173).
 RCCL has no allgatherv; this implements size-exchange + padded allgather,
 with the padding trimmed on unpack (the standard xGMI-friendly schedule:
-one small int64 allgather + one large padded allgather).
+one small int64 allgather + one large padded allgather). The variable-length
+all-to-all (alltoallv) serves ShardedEmbedding's id/vector exchange and the
+owner-routed sparse PS push.
 """
 from typing import List, Tuple
 
@@ -22,11 +24,23 @@ def allgatherv(tensor: torch.Tensor, world_size: int, group=None,
     """
     if world_size <= 1 and not force:
         return [tensor]
+    return _allgather_padded(tensor, _exchange_sizes(tensor, world_size, group),
+                             world_size, group)
+
+
+def _exchange_sizes(tensor: torch.Tensor, world_size: int, group=None
+                    ) -> List[int]:
+    """Every rank's dim-0 length of `tensor`, as host ints."""
     n_local = torch.tensor([tensor.shape[0]], dtype=torch.int64,
                            device=tensor.device)
     sizes = torch.zeros(world_size, dtype=torch.int64, device=tensor.device)
     dist.all_gather_into_tensor(sizes, n_local, group=group)
-    sizes_l = sizes.tolist()
+    return sizes.tolist()
+
+
+def _allgather_padded(tensor: torch.Tensor, sizes_l: List[int],
+                      world_size: int, group=None) -> List[torch.Tensor]:
+    """Padded allgather of `tensor` given every rank's dim-0 length."""
     max_n = max(sizes_l) if sizes_l else 0
     if max_n == 0:
         return [tensor[:0] for _ in range(world_size)]
@@ -46,9 +60,50 @@ def allgather_sparse(indices: torch.Tensor, values: torch.Tensor,
                      ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Gather a row-sparse gradient (indices [nnz], values [nnz, dim...])
     from all ranks; returns concatenated (indices, values)."""
-    idx_parts = allgatherv(indices, world_size, group, force=force)
-    val_parts = allgatherv(values, world_size, group, force=force)
+    idx_parts, val_parts, _ = allgather_rows(indices, values, world_size,
+                                             group, force=force)
     return torch.cat(idx_parts), torch.cat(val_parts)
+
+
+def allgather_rows(indices: torch.Tensor, values: torch.Tensor,
+                   world_size: int, group=None, force: bool = False
+                   ) -> Tuple[List[torch.Tensor], List[torch.Tensor],
+                              List[int]]:
+    """allgatherv of (indices [n], values [n, dim...]) pairs with ONE size
+    exchange for both. Returns (per-rank indices, per-rank values, per-rank
+    row counts); the counts are host ints, so callers can account traffic
+    without another synchronisation."""
+    if world_size <= 1 and not force:
+        return [indices], [values], [int(indices.shape[0])]
+    sizes_l = _exchange_sizes(indices, world_size, group)
+    return (_allgather_padded(indices, sizes_l, world_size, group),
+            _allgather_padded(values, sizes_l, world_size, group), sizes_l)
+
+
+def alltoallv(parts, world, group, trailing_shape=(), recv_sizes=None):
+    """Exchange variable-length dim-0 chunks; parts[r] goes to rank r.
+    Returns (received chunks as a list per source rank, their lengths).
+    `recv_sizes` (the lengths returned by an earlier call whose parts had the
+    same dim-0 lengths, e.g. the ids that go with these values) skips the
+    size exchange."""
+    dev = parts[0].device
+    send_list = [int(p.shape[0]) for p in parts]
+    if recv_sizes is None:
+        send_sizes = torch.tensor(send_list, dtype=torch.int64).to(dev)
+        recv_sizes_t = torch.zeros_like(send_sizes)
+        dist.all_to_all_single(recv_sizes_t, send_sizes, group=group)
+        recv_list = recv_sizes_t.tolist()
+    else:
+        recv_list = list(recv_sizes)
+    total_recv = sum(recv_list)
+    flat_send = torch.cat(parts, dim=0)
+    out = torch.empty((total_recv,) + tuple(trailing_shape),
+                      dtype=flat_send.dtype, device=dev)
+    dist.all_to_all_single(out, flat_send, recv_list, send_list, group=group)
+    offs = [0]
+    for n in recv_list:
+        offs.append(offs[-1] + n)
+    return [out[offs[r]:offs[r + 1]] for r in range(world)], recv_list
 
 
 def coalesce_rows(indices: torch.Tensor, values: torch.Tensor

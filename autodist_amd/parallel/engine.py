@@ -18,7 +18,11 @@ directly:
   * Partitioned vars -> per-shard owners/buckets (partitioner.py semantics).
   * Sparse vars      -> variable-length allgather + segment-coalesce + rowwise
                         apply (reference: all_reduce_synchronizer.py:132-173,
-                        ps_synchronizer.py:476-535).
+                        ps_synchronizer.py:476-535); with
+                        sparse_routing="owner" on a synchronous PS: rows are
+                        pushed to their shard owner (all-to-all), applied
+                        there with shard-local state, and the updated rows
+                        pulled back (allgatherv).
 
 The engine applies optimizer updates itself (parallel/apply.py) — required
 for shard-local state — matching torch.optim numerics exactly.
@@ -34,9 +38,11 @@ from autodist_amd.const import DEFAULT_BUCKET_BYTES, DEFAULT_MASTER_ADDR, \
     DEFAULT_MASTER_PORT
 from autodist_amd.parallel import apply as apply_mod
 from autodist_amd.parallel.buckets import Bucket, build_buckets
-from autodist_amd.parallel.comm import allgather_sparse, coalesce_rows
+from autodist_amd.parallel.comm import allgather_rows, alltoallv, \
+    coalesce_rows
 from autodist_amd.parallel.compressor import Compressor
-from autodist_amd.parallel.partitioner import ShardSlice, make_shard_slices
+from autodist_amd.parallel.partitioner import ShardSlice, \
+    make_shard_slices, sorted_row_segments
 from autodist_amd.proto.strategy_ir import CompressorType
 from autodist_amd.utils import logging
 
@@ -51,6 +57,7 @@ class ShardPlan:
     sync: bool = True
     staleness: int = 0
     local_replication: bool = False
+    sparse_routing: str = "replicated"   # PS only: "replicated" | "owner"
     # runtime state
     state: Optional[dict] = None           # optimizer state (applier ranks)
     master: Optional[torch.Tensor] = None  # PS master copy (owner)
@@ -71,6 +78,8 @@ class VarPlan:
     group_index: int = 0           # index into optimizer.param_groups
     shards: List[ShardPlan] = dataclasses.field(default_factory=list)
     bucketed: bool = False
+    routed: bool = False           # sparse var on the owner-routed PS path
+    shard_edges: Optional[torch.Tensor] = None  # routed: shard starts + end
 
 
 class ShardReducer:
@@ -179,6 +188,9 @@ class DistributedEngine:
         self.ps_groups: list = []
         self._replica_ranks: Dict[str, int] = {}
         self._step_count = 0
+        # logical rows this rank received from OTHER ranks in the last
+        # step's sparse sync (padding excluded); see stats()
+        self._sparse_rows_received = 0
         self._fallback_user_opt = False
         self._setup_done = False
         self._accumulating = False
@@ -367,6 +379,8 @@ class DistributedEngine:
             else:
                 plan.shards.append(self._make_shard(node, None,
                                                     param=item.param))
+            if plan.sparse:
+                plan.routed = self._sparse_routing_applies(plan)
             self.var_plans.append(plan)
         known = {p.name for p in self.var_plans}
         missing = [n for n in vars_by_name if n not in known
@@ -404,9 +418,36 @@ class DistributedEngine:
             return ShardPlan(name=node.var_name, kind="ps", slice=sl,
                              owner_rank=self._owner_rank_of(s.reduction_destination),
                              sync=s.sync, staleness=s.staleness,
-                             local_replication=s.local_replication)
+                             local_replication=s.local_replication,
+                             sparse_routing=s.sparse_routing)
         # no synchronizer: local-only (treated as AR group 0 w/o collective)
         return ShardPlan(name=node.var_name, kind="allreduce", slice=sl)
+
+    def _sparse_routing_applies(self, plan: VarPlan) -> bool:
+        """Does this sparse variable take the owner-routed PS path? Only a
+        fully synchronous PS placement with real collectives does; stale or
+        async PS, allreduce-kind shards and world 1 without forced
+        collectives keep the replicated path."""
+        if not any(sh.kind == "ps" and sh.sparse_routing == "owner"
+                   for sh in plan.shards):
+            return False
+        reason = None
+        if not all(sh.kind == "ps" and sh.sparse_routing == "owner"
+                   for sh in plan.shards):
+            reason = "not every shard is an owner-routed PS shard"
+        elif not all(sh.sync and sh.staleness == 0 for sh in plan.shards):
+            reason = "stale/async PS"
+        elif any(sh.slice is not None and sh.slice.axis != 0
+                 for sh in plan.shards):
+            reason = "shards are not split along the row axis"
+        elif not self.collectives_active:
+            reason = "no collectives at world size 1"
+        if reason is not None:
+            logging.info("sparse var %s: owner routing requested but not "
+                         "applicable (%s); using the replicated path",
+                         plan.name, reason)
+            return False
+        return True
 
     def _sync_initial_params(self):
         if not self.collectives_active:
@@ -605,9 +646,13 @@ class DistributedEngine:
             for sh in plan.shards:
                 if sh.reducer is not None:
                     sh.reducer.finalize(self)
-        # 3) sparse path
+        # 3) sparse path (var_plans order: the same collective sequence on
+        #    every rank)
+        self._sparse_rows_received = 0
         for plan in self.var_plans:
-            if plan.sparse:
+            if plan.routed:
+                self._sync_and_apply_sparse_routed(plan)
+            elif plan.sparse:
                 self._sync_and_apply_sparse(plan)
         # 4) PS rounds: one reduce+apply+broadcast per owner group (those
         #    already hook-issued just complete; the rest flush here)
@@ -679,10 +724,9 @@ class DistributedEngine:
             torch.cuda.synchronize(self.device)
 
     # -- sparse path ---------------------------------------------------------
-    def _sync_and_apply_sparse(self, plan: VarPlan):
-        grad = plan.param.grad
-        if grad is None:
-            return
+    @staticmethod
+    def _sparse_grad_rows(grad):
+        """(row ids, row values) of a sparse-flagged variable's gradient."""
         if grad.is_sparse:
             # use the RAW (possibly duplicated) rows: torch's coalesce() is
             # a full sort pass (rocprim radix/merge sorts were 37% of the
@@ -693,13 +737,22 @@ class DistributedEngine:
             # dense grad on a sparse-flagged var: treat all rows as touched
             indices = torch.arange(grad.shape[0], device=grad.device)
             values = grad
+        return indices, values
+
+    def _sync_and_apply_sparse(self, plan: VarPlan):
+        grad = plan.param.grad
+        if grad is None:
+            return
+        indices, values = self._sparse_grad_rows(grad)
         # weight BEFORE the gather so uneven batch splits produce the exact
         # weighted average after cross-rank coalesce (c0.py:92-119 semantics)
         values = values * self.grad_scale()
         if self.collectives_active:
-            indices, values = allgather_sparse(
+            idx_parts, val_parts, sizes = allgather_rows(
                 indices, values, self.world_size, self.process_group,
                 force=self._force_collectives)
+            self._sparse_rows_received += sum(sizes) - sizes[self.rank]
+            indices, values = torch.cat(idx_parts), torch.cat(val_parts)
         indices, values = coalesce_rows(indices, values)
         # replicated rowwise apply: identical on every rank == PS result
         sh = plan.shards[0]
@@ -711,6 +764,86 @@ class DistributedEngine:
             cls = "SparseAdam"
         apply_mod.apply_sparse_rows(cls, plan.param.data, indices, values,
                                     sh.state, plan.hyper)
+
+    def _sync_and_apply_sparse_routed(self, plan: VarPlan):
+        """Owner-routed sparse PS round: push rows to their shard owners,
+        apply there with shard-local state, pull the updated rows back.
+
+        Wire volume per rank is its own coalesced rows out plus the owners'
+        unique updated rows in, instead of every rank's raw rows; optimizer
+        state exists only on shard owners. Replicas stay bit-identical: an
+        owner's rows are what every other rank copies."""
+        grad = plan.param.grad
+        if grad is None:
+            return
+        world, group = self.world_size, self.process_group
+        param = plan.param.data
+        nrows = param.shape[0]
+        indices, values = self._sparse_grad_rows(grad)
+        # 1) weight (uneven batch splits), then dedup locally so each rank
+        #    pushes a row at most once; coalesced ids come out sorted
+        values = values * self.grad_scale()
+        indices, values = coalesce_rows(indices, values)
+        # 2) push: sorted ids make every shard one contiguous segment; a
+        #    rank's part is the concatenation of the segments it owns
+        if plan.shard_edges is None:
+            edges = [sh.slice.start if sh.slice else 0 for sh in plan.shards]
+            last = plan.shards[-1].slice
+            edges.append(last.end if last else nrows)
+            plan.shard_edges = torch.tensor(edges, dtype=torch.int64,
+                                            device=indices.device)
+        segments = sorted_row_segments(indices, plan.shard_edges)
+        per_rank: List[list] = [[] for _ in range(world)]
+        for sh, seg in zip(plan.shards, segments):
+            per_rank[sh.owner_rank].append(seg)
+        id_parts, val_parts = [], []
+        for segs in per_rank:
+            if len(segs) == 1:
+                lo, hi = segs[0]
+                id_parts.append(indices[lo:hi])
+                val_parts.append(values[lo:hi])
+            else:  # none (empty part) or several owned shards
+                id_parts.append(torch.cat(
+                    [indices[lo:hi] for lo, hi in segs] or [indices[:0]]))
+                val_parts.append(torch.cat(
+                    [values[lo:hi] for lo, hi in segs] or [values[:0]]))
+        recv_ids, counts = alltoallv(id_parts, world, group)
+        recv_vals, _ = alltoallv(val_parts, world, group,
+                                 trailing_shape=tuple(values.shape[1:]),
+                                 recv_sizes=counts)
+        self._sparse_rows_received += sum(counts) - counts[self.rank]
+        # 3) owner: sum what the ranks pushed, then one row-wise apply per
+        #    owned shard. Every owned shard is applied EVERY step, rows or
+        #    not: its step counter is the global step (Adagrad lr_decay, Adam
+        #    bias correction), exactly as the replicated path advances it.
+        own_ids, own_vals = coalesce_rows(torch.cat(recv_ids),
+                                          torch.cat(recv_vals))
+        own_vals = own_vals.contiguous()
+        new_rows = torch.empty_like(own_vals)
+        cls = plan.cls_name
+        if cls == "Adam" and plan.hyper.get("_sparse_adam"):
+            cls = "SparseAdam"
+        for sh in plan.shards:
+            if sh.owner_rank != self.rank:
+                continue  # non-owners hold no state for this shard
+            view = sh.slice.view(param) if sh.slice else param
+            if sh.state is None:
+                sh.state = apply_mod.make_state(plan.cls_name, view,
+                                                plan.hyper)
+            # ids of other owned shards fall outside [start, start+len) and
+            # are skipped; each shard fills its own rows of new_rows
+            apply_mod.apply_sparse_rows(
+                cls, view, own_ids, own_vals, sh.state, plan.hyper,
+                row_base=sh.slice.start if sh.slice else 0,
+                new_rows=new_rows)
+        # 4) pull: owners publish (global ids, updated rows); every other
+        #    rank copies them into its replica bit for bit
+        idx_parts, row_parts, sizes = allgather_rows(
+            own_ids, new_rows, world, group, force=self._force_collectives)
+        self._sparse_rows_received += sum(sizes) - sizes[self.rank]
+        for r in range(world):
+            if r != self.rank and sizes[r]:
+                param.index_copy_(0, idx_parts[r], row_parts[r])
 
     # ----------------------------------------------------- checkpoint support
     def _state_keys(self, cls_name: str, hyper: dict):
@@ -792,10 +925,10 @@ class DistributedEngine:
                     parts = allgatherv(t.detach().contiguous(),
                                        self.world_size, self.process_group)
                     state[k] = torch.cat(parts, dim=0).cpu()
-            elif plan.sparse or (len(plan.shards) == 1
-                                 and plan.shards[0].kind in ("allreduce",
-                                                             "local")
-                                 and plan.shards[0].slice is None):
+            elif (plan.sparse and not plan.routed) or (
+                    len(plan.shards) == 1
+                    and plan.shards[0].kind in ("allreduce", "local")
+                    and plan.shards[0].slice is None):
                 sh = plan.shards[0]
                 if sh.state:
                     for k in keys:
@@ -905,9 +1038,11 @@ class DistributedEngine:
             else:
                 axis = plan.shards[0].slice.axis if plan.shards[0].slice else 0
                 for sh in plan.shards:
+                    # replicated sparse vars apply on every rank; routed
+                    # ones only on the shard owner, with the shard's slice
                     applies_here = (sh.kind == "allreduce"
                                     or self.rank == sh.owner_rank
-                                    or plan.sparse)
+                                    or (plan.sparse and not plan.routed))
                     if not applies_here:
                         continue
                     ref = sh.master if sh.master is not None else (
@@ -967,6 +1102,8 @@ class DistributedEngine:
             "partitioned_ar_shards": n_reducers,
             "partitioned_ar_bytes_per_step": shard_reduce_bytes,
             "sparse_vars": sum(1 for p in self.var_plans if p.sparse),
+            "sparse_routed_vars": sum(1 for p in self.var_plans if p.routed),
+            "sparse_rows_received_last_step": self._sparse_rows_received,
             "fallback_user_optimizer": self._fallback_user_opt,
         }
 

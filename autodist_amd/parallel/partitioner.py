@@ -67,6 +67,20 @@ def make_shard_slices(shape, partitioner: str) -> List[ShardSlice]:
     return [ShardSlice(axis, s, e) for s, e in split_boundaries(shape[axis], n)]
 
 
+def sorted_row_segments(sorted_ids: torch.Tensor, edges: torch.Tensor
+                        ) -> List[Tuple[int, int]]:
+    """Per-shard [lo, hi) positions inside SORTED global row ids.
+
+    `edges` holds the shards' first rows followed by the last shard's end
+    (len = n_shards + 1, ascending, same device as the ids). Sorted ids make
+    every shard one contiguous segment, so routing is a binary search per
+    edge and one host read instead of route_sparse_rows' mask per shard; ids
+    outside [edges[0], edges[-1]) fall in no segment.
+    """
+    cuts = torch.searchsorted(sorted_ids, edges).tolist()
+    return list(zip(cuts[:-1], cuts[1:]))
+
+
 def route_sparse_rows(indices: torch.Tensor, values: torch.Tensor,
                       slices: List[ShardSlice]):
     """Route sparse gradient rows to shards with index rebasing

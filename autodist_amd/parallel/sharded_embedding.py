@@ -18,8 +18,8 @@ At world_size==1 this degrades to a plain local gather.
 from typing import Optional
 
 import torch
-import torch.distributed as dist
 
+from autodist_amd.parallel.comm import alltoallv as _alltoallv
 from autodist_amd.parallel.partitioner import split_boundaries
 
 
@@ -28,27 +28,6 @@ def _forced() -> bool:
     world 1 (1-GPU RCCL hardware validation; identity routing)."""
     import os
     return os.environ.get("AUTODIST_FORCE_COLLECTIVES", "") in ("1", "True")
-
-
-def _alltoallv(parts, world, group, trailing_shape=()):
-    """Exchange variable-length dim-0 chunks; parts[r] goes to rank r.
-    Returns received chunks (list per source rank)."""
-    send_sizes = torch.tensor([p.shape[0] for p in parts], dtype=torch.int64)
-    dev = parts[0].device
-    send_sizes = send_sizes.to(dev)
-    recv_sizes = torch.zeros_like(send_sizes)
-    dist.all_to_all_single(recv_sizes, send_sizes, group=group)
-    recv_list = recv_sizes.tolist()
-    send_list = [int(p.shape[0]) for p in parts]
-    total_recv = sum(recv_list)
-    flat_send = torch.cat(parts, dim=0)
-    out = torch.empty((total_recv,) + tuple(trailing_shape),
-                      dtype=flat_send.dtype, device=dev)
-    dist.all_to_all_single(out, flat_send, recv_list, send_list, group=group)
-    offs = [0]
-    for n in recv_list:
-        offs.append(offs[-1] + n)
-    return [out[offs[r]:offs[r + 1]] for r in range(world)], recv_list
 
 
 class _ShardedLookup(torch.autograd.Function):

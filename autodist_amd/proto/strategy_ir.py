@@ -33,6 +33,9 @@ class CompressorType(enum.IntEnum):
     PowerSGDCompressor = 3
 
 
+SPARSE_ROUTING_MODES = ("replicated", "owner")
+
+
 @dataclasses.dataclass
 class PSSynchronizer:
     """Parameter-server sync config (synchronizers.proto:26-31)."""
@@ -40,11 +43,24 @@ class PSSynchronizer:
     local_replication: bool = False   # proxy-variable caching on each worker
     sync: bool = True                 # synchronous (True) vs async (False)
     staleness: int = 0                # bounded staleness k (sync must be True)
+    # Addition over the reference proto: how SPARSE variables reach this PS.
+    # "replicated" = every rank allgathers all rows and applies the full
+    # update itself; "owner" = rows are pushed to the shard owner, which
+    # applies them with shard-local state and the updated rows are pulled
+    # back. Dense variables ignore it.
+    sparse_routing: str = "replicated"
+
+    def __post_init__(self):
+        if self.sparse_routing not in SPARSE_ROUTING_MODES:
+            raise ValueError(
+                f"sparse_routing must be one of {SPARSE_ROUTING_MODES}, "
+                f"got {self.sparse_routing!r}")
 
     def to_dict(self):
         return {"reduction_destination": self.reduction_destination,
                 "local_replication": self.local_replication,
-                "sync": self.sync, "staleness": self.staleness}
+                "sync": self.sync, "staleness": self.staleness,
+                "sparse_routing": self.sparse_routing}
 
     @classmethod
     def from_dict(cls, d):

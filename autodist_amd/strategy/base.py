@@ -5,8 +5,9 @@ Reference behavior: autodist/strategy/base.py:28-168.
 import os
 from datetime import datetime
 
-from autodist_amd.const import DEFAULT_SERIALIZATION_DIR
-from autodist_amd.proto.strategy_ir import GraphConfig, StrategyProto
+from autodist_amd.const import DEFAULT_SERIALIZATION_DIR, ENV
+from autodist_amd.proto.strategy_ir import (SPARSE_ROUTING_MODES, GraphConfig,
+                                            StrategyProto)
 from autodist_amd.utils import logging
 
 
@@ -69,6 +70,18 @@ class Strategy:
 
     def __str__(self):
         return str(self._proto)
+
+
+def resolve_sparse_routing(value=None) -> str:
+    """PS builders' `sparse_routing` keyword: None reads the
+    AUTODIST_SPARSE_PS_ROUTING flag (default "replicated"), so benchmarks and
+    examples can exercise the owner-routed sparse path unedited."""
+    if value is None:
+        value = ENV.AUTODIST_SPARSE_PS_ROUTING.val
+    if value not in SPARSE_ROUTING_MODES:
+        raise ValueError(f"sparse_routing must be one of "
+                         f"{SPARSE_ROUTING_MODES}, got {value!r}")
+    return value
 
 
 class StrategyBuilder:

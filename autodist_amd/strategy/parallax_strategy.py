@@ -20,8 +20,10 @@ class Parallax(PSLoadBalancing):
     """Hybrid per-variable AR/PS mixing (reference parallax_strategy.py:38-71)."""
 
     def __init__(self, chunk_size=128, local_proxy_variable=False, sync=True,
-                 staleness=0, all_reduce_spec="RCCL", compressor="NoneCompressor"):
-        super().__init__(local_proxy_variable, sync, staleness)
+                 staleness=0, all_reduce_spec="RCCL", compressor="NoneCompressor",
+                 sparse_routing=None):
+        super().__init__(local_proxy_variable, sync, staleness,
+                         sparse_routing=sparse_routing)
         self.chunk_size = chunk_size
         self.all_reduce_spec = all_reduce_spec
         self.compressor = compressor
@@ -46,7 +48,8 @@ class Parallax(PSLoadBalancing):
                 configs.append(Node(var_name=v.name, ps_synchronizer=PSSynchronizer(
                     reduction_destination=device,
                     local_replication=self._local_proxy_variable,
-                    sync=self._sync, staleness=self._staleness)))
+                    sync=self._sync, staleness=self._staleness,
+                    sparse_routing=self._sparse_routing)))
             else:
                 configs.append(Node(
                     var_name=v.name,

@@ -9,7 +9,8 @@ all 7 xGMI links of every GPU and shards optimizer state (each owner holds
 only its shard's momentum/Adam state).
 """
 from autodist_amd.proto.strategy_ir import Node, PSSynchronizer
-from autodist_amd.strategy.base import Strategy, StrategyBuilder
+from autodist_amd.strategy.base import (Strategy, StrategyBuilder,
+                                        resolve_sparse_routing)
 from autodist_amd.strategy.ps_lb_strategy import byte_size_load_fn
 
 
@@ -28,10 +29,12 @@ class PartitionedPS(StrategyBuilder):
     """Axis-0 partition + load-balanced PS placement
     (reference partitioned_ps_strategy.py:42-123)."""
 
-    def __init__(self, local_proxy_variable=False, sync=True, staleness=0):
+    def __init__(self, local_proxy_variable=False, sync=True, staleness=0,
+                 sparse_routing=None):
         self._local_proxy_variable = local_proxy_variable
         self._sync = sync
         self._staleness = staleness
+        self._sparse_routing = resolve_sparse_routing(sparse_routing)
         if staleness > 0:
             assert sync, "staleness is only valid for sync training"
         self.loads = {}
@@ -65,7 +68,8 @@ class PartitionedPS(StrategyBuilder):
             return Node(var_name=var_item.name, ps_synchronizer=PSSynchronizer(
                 reduction_destination=self._pick_device(byte_size_load_fn(var_item)),
                 local_replication=self._local_proxy_variable,
-                sync=self._sync, staleness=self._staleness))
+                sync=self._sync, staleness=self._staleness,
+                sparse_routing=self._sparse_routing))
         # partitioner string "n,1,1,..." = n shards along axis 0
         partitioner = ",".join([str(n_shards)] + ["1"] * (len(var_item.shape) - 1))
         shard_load = byte_size_load_fn(var_item) / n_shards
@@ -76,7 +80,8 @@ class PartitionedPS(StrategyBuilder):
                 ps_synchronizer=PSSynchronizer(
                     reduction_destination=self._pick_device(shard_load),
                     local_replication=self._local_proxy_variable,
-                    sync=self._sync, staleness=self._staleness)))
+                    sync=self._sync, staleness=self._staleness,
+                    sparse_routing=self._sparse_routing)))
         return Node(var_name=var_item.name, partitioner=partitioner,
                     part_config=parts)
 

@@ -7,7 +7,8 @@ set is every GPU (one rank per GPU) — sharding parameter ownership across all
 optimizer-state memory (ZeRO-style), instead of packing onto per-node CPUs.
 """
 from autodist_amd.proto.strategy_ir import Node, PSSynchronizer
-from autodist_amd.strategy.base import Strategy, StrategyBuilder
+from autodist_amd.strategy.base import (Strategy, StrategyBuilder,
+                                        resolve_sparse_routing)
 
 
 def byte_size_load_fn(var_item) -> float:
@@ -19,10 +20,12 @@ class PSLoadBalancing(StrategyBuilder):
     """Greedy least-loaded assignment of vars to PS devices
     (reference ps_lb_strategy.py:42-86)."""
 
-    def __init__(self, local_proxy_variable=False, sync=True, staleness=0):
+    def __init__(self, local_proxy_variable=False, sync=True, staleness=0,
+                 sparse_routing=None):
         self._local_proxy_variable = local_proxy_variable
         self._sync = sync
         self._staleness = staleness
+        self._sparse_routing = resolve_sparse_routing(sparse_routing)
         if staleness > 0:
             assert sync, "staleness is only valid for sync training"
         self.loads = {}
@@ -46,4 +49,5 @@ class PSLoadBalancing(StrategyBuilder):
         return Node(var_name=var_item.name, ps_synchronizer=PSSynchronizer(
             reduction_destination=device,
             local_replication=self._local_proxy_variable,
-            sync=self._sync, staleness=self._staleness))
+            sync=self._sync, staleness=self._staleness,
+            sparse_routing=self._sparse_routing))

@@ -7,16 +7,19 @@ xGMI links (~153 GB/s/link) instead of staging through host memory, and the
 update runs on-device. The CPU destination is kept for CPU-only topologies.
 """
 from autodist_amd.proto.strategy_ir import Node, PSSynchronizer
-from autodist_amd.strategy.base import Strategy, StrategyBuilder
+from autodist_amd.strategy.base import (Strategy, StrategyBuilder,
+                                        resolve_sparse_routing)
 
 
 class PS(StrategyBuilder):
     """All variables on a single PS (reference ps_strategy.py:37-56)."""
 
-    def __init__(self, local_proxy_variable=False, sync=True, staleness=0):
+    def __init__(self, local_proxy_variable=False, sync=True, staleness=0,
+                 sparse_routing=None):
         self._local_proxy_variable = local_proxy_variable
         self._sync = sync
         self._staleness = staleness
+        self._sparse_routing = resolve_sparse_routing(sparse_routing)
         if staleness > 0:
             assert sync, "staleness is only valid for sync training"
 
@@ -40,4 +43,5 @@ class PS(StrategyBuilder):
         return Node(var_name=var_name, ps_synchronizer=PSSynchronizer(
             reduction_destination=reduction_device,
             local_replication=self._local_proxy_variable,
-            sync=self._sync, staleness=self._staleness))
+            sync=self._sync, staleness=self._staleness,
+            sparse_routing=self._sparse_routing))
