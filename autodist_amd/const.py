@@ -49,6 +49,7 @@ class ENV(enum.Enum):
     AUTODIST_RANK = ((lambda v: int(v) if v else None),)            # explicit rank override
     AUTODIST_RESOURCE_SPEC = ((lambda v: v or ""),)                 # path to resource spec yaml
     AUTODIST_SPARSE_PS_ROUTING = ((lambda v: v or "replicated"),)   # PS builders' default sparse_routing ("replicated" | "owner")
+    AUTODIST_DENSE_AR_SCHEDULE = ((lambda v: v or "allreduce"),)    # AllReduce/Parallax builders' default schedule ("allreduce" | "sharded")
 
     @property
     def val(self):

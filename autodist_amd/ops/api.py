@@ -145,6 +145,86 @@ def fused_apply(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
     return False
 
 
+_WIRE_CLASSES = ("SGD", "Adam", "AdamW", "Adagrad")
+
+
+def _wire_ok(t: torch.Tensor, dtype: torch.dtype, n: int) -> bool:
+    return (t.is_cuda and t.dtype == dtype and t.is_contiguous()
+            and t.numel() == n and t.data_ptr() % 16 == 0)
+
+
+def fused_apply_wire(cls_name: str, param: torch.Tensor,
+                     grad_bf16: torch.Tensor, state: dict,
+                     hyper: dict) -> bool:
+    """fused_apply for a bf16 gradient: the optimizer kernel reads the
+    reduce-scattered bf16 wire shard directly and widens it in registers, so
+    the sharded dense schedule never casts the shard back to fp32. Bit-equal
+    to cast_back_f32 + fused_apply (the widening is exact, the arithmetic is
+    the same code). Step and bias-correction handling as in fused_apply.
+
+    Returns False, with `state` untouched, when there is no wire kernel for
+    this class / flag combination (RMSprop, amsgrad, the non-fused classes)
+    or the tensors are not contiguous, 16-byte aligned fp32 / bf16 GPU
+    tensors of one length; the check is host-side and nothing is launched."""
+    if cls_name not in _WIRE_CLASSES or not fused_supported(cls_name, hyper):
+        return False
+    e = _load() if param.is_cuda else None
+    if e is None:
+        return False
+    n = param.numel()
+    if not (_wire_ok(param, torch.float32, n)
+            and _wire_ok(grad_bf16, torch.bfloat16, n)):
+        return False
+    if cls_name == "SGD":
+        momentum = float(hyper.get("momentum", 0.0))
+        buf = state.get("momentum_buffer") if momentum != 0.0 else None
+        if buf is not None and not _wire_ok(buf, torch.float32, n):
+            return False
+        first = False
+        if momentum != 0.0 and buf is None:
+            buf = state["momentum_buffer"] = torch.empty_like(
+                param, memory_format=torch.contiguous_format)
+            first = True
+        e.fused_sgd_wire(param, grad_bf16, buf, float(hyper["lr"]), momentum,
+                         float(hyper.get("dampening", 0.0)),
+                         float(hyper.get("weight_decay", 0.0)),
+                         bool(hyper.get("nesterov", False)), first,
+                         bool(hyper.get("maximize", False)))
+        return True
+    if cls_name in ("Adam", "AdamW"):
+        if not (_wire_ok(state["exp_avg"], torch.float32, n)
+                and _wire_ok(state["exp_avg_sq"], torch.float32, n)):
+            return False
+        state["step"] += 1
+        step = float(state["step"])
+        beta1, beta2 = hyper.get("betas", (0.9, 0.999))
+        bc1 = 1.0 - beta1 ** step
+        sqrt_bc2 = (1.0 - beta2 ** step) ** 0.5
+        wd_default = 0.01 if cls_name == "AdamW" else 0.0
+        decoupled = cls_name == "AdamW" or bool(
+            hyper.get("decoupled_weight_decay", False))
+        e.fused_adam_wire(param, grad_bf16, state["exp_avg"],
+                          state["exp_avg_sq"], float(hyper["lr"]),
+                          float(beta1), float(beta2),
+                          float(hyper.get("eps", 1e-8)),
+                          float(hyper.get("weight_decay", wd_default)),
+                          decoupled, bc1, sqrt_bc2,
+                          bool(hyper.get("maximize", False)))
+        return True
+    # Adagrad
+    if not _wire_ok(state["sum"], torch.float32, n):
+        return False
+    state["step"] += 1
+    clr = float(hyper["lr"]) / (
+        1.0 + (float(state["step"]) - 1.0)
+        * float(hyper.get("lr_decay", 0.0)))
+    e.fused_adagrad_wire(param, grad_bf16, state["sum"], clr,
+                         float(hyper.get("eps", 1e-10)),
+                         float(hyper.get("weight_decay", 0.0)),
+                         bool(hyper.get("maximize", False)))
+    return True
+
+
 _SPARSE_FUSED_IDS = {"SGD": 0, "Adagrad": 1, "Adam": 2, "AdamW": 2,
                      "SparseAdam": 2}
 

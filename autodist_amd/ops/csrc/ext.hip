@@ -259,27 +259,67 @@ void check_f32_flat(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
 }
 
+// The launchers are shared by the fp32-gradient entry points and by the
+// *_wire entry points, whose gradient is the bf16 wire shard of the sharded
+// dense schedule (multi_tensor.hip, "gradient stream").
+template <typename GT>
+void launch_fused_sgd(torch::Tensor& p, const GT* g,
+                      c10::optional<torch::Tensor>& buf, double lr,
+                      double momentum, double dampening, double weight_decay,
+                      bool nesterov, bool first_step, bool maximize) {
+  long n = p.numel();
+  dim3 grid(grid_for(n)), block(BLOCK_THREADS);
+  if (buf.has_value()) {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_sgd_kernel<true, GT>), grid,
+                       block, 0, cur_stream(), p.data_ptr<float>(), g,
+                       buf->data_ptr<float>(), n, (float)lr, (float)momentum,
+                       (float)(1.0 - dampening), (float)weight_decay, nesterov,
+                       first_step, maximize);
+  } else {
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_sgd_kernel<false, GT>), grid,
+                       block, 0, cur_stream(), p.data_ptr<float>(), g,
+                       nullptr, n, (float)lr, (float)momentum,
+                       (float)(1.0 - dampening), (float)weight_decay, nesterov,
+                       first_step, maximize);
+  }
+}
+
+template <typename GT>
+void launch_fused_adam(torch::Tensor& p, const GT* g, torch::Tensor& m,
+                       torch::Tensor& v, double lr, double beta1, double beta2,
+                       double eps, double weight_decay, bool adamw, double bc1,
+                       double sqrt_bc2, bool maximize) {
+  long n = p.numel();
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_adam_kernel<GT>),
+                     dim3(grid_for(n)), dim3(BLOCK_THREADS), 0, cur_stream(),
+                     p.data_ptr<float>(), g, m.data_ptr<float>(),
+                     v.data_ptr<float>(), n, (float)lr, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                     (float)eps, (float)weight_decay, adamw, (float)bc1,
+                     (float)sqrt_bc2, maximize);
+}
+
+template <typename GT>
+void launch_fused_adagrad(torch::Tensor& p, const GT* g, torch::Tensor& sum,
+                          double clr, double eps, double weight_decay,
+                          bool maximize) {
+  long n = p.numel();
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(fused_adagrad_kernel<GT>),
+                     dim3(grid_for(n)), dim3(BLOCK_THREADS), 0, cur_stream(),
+                     p.data_ptr<float>(), g, sum.data_ptr<float>(), n,
+                     (float)clr, (float)eps, (float)weight_decay, maximize);
+}
+
 void fused_sgd(torch::Tensor p, torch::Tensor g,
                c10::optional<torch::Tensor> buf, double lr, double momentum,
                double dampening, double weight_decay, bool nesterov,
                bool first_step, bool maximize) {
   check_f32_flat(p, "param");
   check_f32_flat(g, "grad");
-  long n = p.numel();
-  dim3 grid(grid_for(n)), block(BLOCK_THREADS);
-  if (buf.has_value()) {
-    check_f32_flat(*buf, "momentum_buffer");
-    hipLaunchKernelGGL(fused_sgd_kernel<true>, grid, block, 0, cur_stream(),
-                       p.data_ptr<float>(), g.data_ptr<float>(),
-                       buf->data_ptr<float>(), n, (float)lr, (float)momentum,
-                       (float)(1.0 - dampening), (float)weight_decay, nesterov,
-                       first_step, maximize);
-  } else {
-    hipLaunchKernelGGL(fused_sgd_kernel<false>, grid, block, 0, cur_stream(),
-                       p.data_ptr<float>(), g.data_ptr<float>(), nullptr, n,
-                       (float)lr, (float)momentum, (float)(1.0 - dampening),
-                       (float)weight_decay, nesterov, first_step, maximize);
-  }
+  if (buf.has_value()) check_f32_flat(*buf, "momentum_buffer");
+  launch_fused_sgd<float>(p, g.data_ptr<float>(), buf, lr, momentum,
+                          dampening, weight_decay, nesterov, first_step,
+                          maximize);
 }
 
 void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
@@ -290,15 +330,8 @@ void fused_adam(torch::Tensor p, torch::Tensor g, torch::Tensor m,
   check_f32_flat(g, "grad");
   check_f32_flat(m, "exp_avg");
   check_f32_flat(v, "exp_avg_sq");
-  long n = p.numel();
-  hipLaunchKernelGGL(fused_adam_kernel, dim3(grid_for(n)),
-                     dim3(BLOCK_THREADS), 0, cur_stream(),
-                     p.data_ptr<float>(), g.data_ptr<float>(),
-                     m.data_ptr<float>(), v.data_ptr<float>(), n, (float)lr,
-                     (float)beta1, (float)beta2, (float)(1.0 - beta1),
-                     (float)(1.0 - beta2), (float)eps,
-                     (float)weight_decay, adamw, (float)bc1, (float)sqrt_bc2,
-                     maximize);
+  launch_fused_adam<float>(p, g.data_ptr<float>(), m, v, lr, beta1, beta2,
+                           eps, weight_decay, adamw, bc1, sqrt_bc2, maximize);
 }
 
 void fused_adagrad(torch::Tensor p, torch::Tensor g, torch::Tensor sum,
@@ -307,12 +340,73 @@ void fused_adagrad(torch::Tensor p, torch::Tensor g, torch::Tensor sum,
   check_f32_flat(p, "param");
   check_f32_flat(g, "grad");
   check_f32_flat(sum, "sum");
+  launch_fused_adagrad<float>(p, g.data_ptr<float>(), sum, clr, eps,
+                              weight_decay, maximize);
+}
+
+// ---- bf16-gradient ("wire") entry points. The vector paths read 16 B per
+// lane from the fp32 streams and 8 B per lane from the bf16 stream at lane
+// offsets that are multiples of 4 elements, so every base pointer must be
+// 16-byte aligned (shard views of a sharded bucket are: shard lengths are
+// multiples of 8 elements). All operands hold the same number of elements.
+void check_aligned16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name,
+              " must be 16-byte aligned");
+}
+
+void check_wire_f32(const torch::Tensor& t, long n, const char* name) {
+  check_f32_flat(t, name);
+  check_aligned16(t, name);
+  TORCH_CHECK(t.numel() == n, name, " must have ", n, " elements, got ",
+              t.numel());
+}
+
+const __hip_bfloat16* check_wire_grad(const torch::Tensor& g, long n) {
+  TORCH_CHECK(g.is_cuda(), "grad must be on GPU");
+  TORCH_CHECK(g.is_contiguous(), "grad must be contiguous");
+  TORCH_CHECK(g.scalar_type() == torch::kBFloat16, "grad must be bf16");
+  check_aligned16(g, "grad");
+  TORCH_CHECK(g.numel() == n, "grad must have ", n, " elements, got ",
+              g.numel());
+  return reinterpret_cast<const __hip_bfloat16*>(g.data_ptr());
+}
+
+void fused_sgd_wire(torch::Tensor p, torch::Tensor g,
+                    c10::optional<torch::Tensor> buf, double lr,
+                    double momentum, double dampening, double weight_decay,
+                    bool nesterov, bool first_step, bool maximize) {
   long n = p.numel();
-  hipLaunchKernelGGL(fused_adagrad_kernel, dim3(grid_for(n)),
-                     dim3(BLOCK_THREADS), 0, cur_stream(),
-                     p.data_ptr<float>(), g.data_ptr<float>(),
-                     sum.data_ptr<float>(), n, (float)clr, (float)eps,
-                     (float)weight_decay, maximize);
+  check_wire_f32(p, n, "param");
+  const __hip_bfloat16* gp = check_wire_grad(g, n);
+  if (buf.has_value()) check_wire_f32(*buf, n, "momentum_buffer");
+  launch_fused_sgd<__hip_bfloat16>(p, gp, buf, lr, momentum, dampening,
+                                   weight_decay, nesterov, first_step,
+                                   maximize);
+}
+
+void fused_adam_wire(torch::Tensor p, torch::Tensor g, torch::Tensor m,
+                     torch::Tensor v, double lr, double beta1, double beta2,
+                     double eps, double weight_decay, bool adamw, double bc1,
+                     double sqrt_bc2, bool maximize) {
+  long n = p.numel();
+  check_wire_f32(p, n, "param");
+  const __hip_bfloat16* gp = check_wire_grad(g, n);
+  check_wire_f32(m, n, "exp_avg");
+  check_wire_f32(v, n, "exp_avg_sq");
+  launch_fused_adam<__hip_bfloat16>(p, gp, m, v, lr, beta1, beta2, eps,
+                                    weight_decay, adamw, bc1, sqrt_bc2,
+                                    maximize);
+}
+
+void fused_adagrad_wire(torch::Tensor p, torch::Tensor g, torch::Tensor sum,
+                        double clr, double eps, double weight_decay,
+                        bool maximize) {
+  long n = p.numel();
+  check_wire_f32(p, n, "param");
+  const __hip_bfloat16* gp = check_wire_grad(g, n);
+  check_wire_f32(sum, n, "sum");
+  launch_fused_adagrad<__hip_bfloat16>(p, gp, sum, clr, eps, weight_decay,
+                                       maximize);
 }
 
 void fused_rmsprop(torch::Tensor p, torch::Tensor g, torch::Tensor sq,
@@ -839,6 +933,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fused_adam", &fused_adam, "fused flat Adam/AdamW update (gfx950)");
   m.def("fused_adagrad", &fused_adagrad,
         "fused flat Adagrad update (gfx950)");
+  m.def("fused_sgd_wire", &fused_sgd_wire,
+        "fused flat SGD update, bf16 wire gradient (gfx950)");
+  m.def("fused_adam_wire", &fused_adam_wire,
+        "fused flat Adam/AdamW update, bf16 wire gradient (gfx950)");
+  m.def("fused_adagrad_wire", &fused_adagrad_wire,
+        "fused flat Adagrad update, bf16 wire gradient (gfx950)");
   m.def("fused_rmsprop", &fused_rmsprop,
         "fused flat RMSprop update (gfx950, centered/momentum variants)");
   m.def("scale_cast_bf16", &scale_cast_bf16, "scale+cast fp32->bf16");

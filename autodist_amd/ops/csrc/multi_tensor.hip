@@ -10,6 +10,50 @@
 #include "common.h"
 #include <cstdint>
 
+// ------------------------------------------- gradient stream: fp32 or bf16
+// The flat SGD / Adam / Adagrad kernels below are templated on the gradient
+// element type GT. GT = float is the ordinary bucket path. GT = __hip_bfloat16
+// reads the reduce-scattered bf16 WIRE shard of the sharded dense schedule
+// directly (parallel/buckets.py): each element is widened to fp32 in
+// registers, which is exact (bf16 is the top 16 bits of an fp32), and the
+// arithmetic that follows is the same code, so the result is bit-identical to
+// cast_back_f32 followed by the fp32 instantiation, without the shard-sized
+// fp32 round trip through HBM.
+//
+// Lane geometry is the same for both: 4 elements per lane per iteration. The
+// fp32 streams (param, state) stay at 16 B/lane; the bf16 stream is 8 B/lane
+// (one dwordx2, 512 B per wave instruction, still fully coalesced). The
+// alternative, 8 elements per lane with a 16 B bf16 load, would double the
+// live fp32 registers of every other stream (Adam: p, m, v) for the stream
+// that carries only 2 of the kernel's 26 bytes per element, and would give
+// the two instantiations different loop bodies; at 4 per lane they share
+// one, which is what keeps them bit-identical by construction.
+__device__ __forceinline__ void load_grad4(const float* __restrict__ g,
+                                           long base, float (&out)[4]) {
+  float4 gv = *reinterpret_cast<const float4*>(g + base);
+  out[0] = gv.x; out[1] = gv.y; out[2] = gv.z; out[3] = gv.w;
+}
+
+__device__ __forceinline__ void load_grad4(
+    const __hip_bfloat16* __restrict__ g, long base, float (&out)[4]) {
+  uint2 gv = *reinterpret_cast<const uint2*>(g + base);
+  out[0] = __uint_as_float(gv.x << 16);
+  out[1] = __uint_as_float(gv.x & 0xffff0000u);
+  out[2] = __uint_as_float(gv.y << 16);
+  out[3] = __uint_as_float(gv.y & 0xffff0000u);
+}
+
+__device__ __forceinline__ float load_grad1(const float* __restrict__ g,
+                                            long i) {
+  return g[i];
+}
+
+__device__ __forceinline__ float load_grad1(
+    const __hip_bfloat16* __restrict__ g, long i) {
+  return __uint_as_float(
+      (unsigned)reinterpret_cast<const unsigned short*>(g)[i] << 16);
+}
+
 // ---------------------------------------------------------------- SGD
 // d = g (+ wd*p); buf = mom*buf + (1-damp)*d (or = d on first step);
 // d = nesterov ? d + mom*buf : buf; p -= lr*d
@@ -18,9 +62,9 @@
 // formed in double on the host and passed in: 1.f - 0.999f is off by 4.7e-5
 // relative (the rounding of 0.999f, magnified 1000x by the subtraction),
 // which moved every Adam update by 2.3e-5 relative to torch.optim.
-template <bool HAS_MOMENTUM>
+template <bool HAS_MOMENTUM, typename GT>
 __global__ void fused_sgd_kernel(float* __restrict__ p,
-                                 const float* __restrict__ g,
+                                 const GT* __restrict__ g,
                                  float* __restrict__ buf, long n, float lr,
                                  float momentum, float one_minus_damp,
                                  float weight_decay, int nesterov,
@@ -30,8 +74,8 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
        base += stride) {
     if (base + 3 < n) {
       float4 pv = *reinterpret_cast<float4*>(p + base);
-      float4 gv = *reinterpret_cast<const float4*>(g + base);
-      float d[4] = {gv.x, gv.y, gv.z, gv.w};
+      float d[4];
+      load_grad4(g, base, d);
       float pr[4] = {pv.x, pv.y, pv.z, pv.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -55,7 +99,8 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
           make_float4(pr[0], pr[1], pr[2], pr[3]);
     } else {
       for (long i = base; i < n; ++i) {
-        float d = maximize ? -g[i] : g[i];
+        float d = load_grad1(g, i);
+        if (maximize) d = -d;
         d += weight_decay * p[i];
         if (HAS_MOMENTUM) {
           float b = first_step ? d : momentum * buf[i] + one_minus_damp * d;
@@ -72,8 +117,9 @@ __global__ void fused_sgd_kernel(float* __restrict__ p,
 // adamw: p *= (1 - lr*wd) else g += wd*p
 // m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g^2
 // p -= lr/bc1 * m / (sqrt(v)/sqrt(bc2) + eps)
+template <typename GT>
 __global__ void fused_adam_kernel(float* __restrict__ p,
-                                  const float* __restrict__ g,
+                                  const GT* __restrict__ g,
                                   float* __restrict__ m, float* __restrict__ v,
                                   long n, float lr, float beta1, float beta2,
                                   float one_minus_beta1,
@@ -88,11 +134,11 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
     long lim = base + 4 <= n ? 4 : n - base;
     if (lim == 4) {
       float4 pv = *reinterpret_cast<float4*>(p + base);
-      float4 gv = *reinterpret_cast<const float4*>(g + base);
       float4 mv = *reinterpret_cast<float4*>(m + base);
       float4 vv = *reinterpret_cast<float4*>(v + base);
       float pr[4] = {pv.x, pv.y, pv.z, pv.w};
-      float gr[4] = {gv.x, gv.y, gv.z, gv.w};
+      float gr[4];
+      load_grad4(g, base, gr);
       float mr[4] = {mv.x, mv.y, mv.z, mv.w};
       float vr[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
@@ -108,7 +154,8 @@ __global__ void fused_adam_kernel(float* __restrict__ p,
       *reinterpret_cast<float4*>(v + base) = make_float4(vr[0], vr[1], vr[2], vr[3]);
     } else {
       for (long i = base; i < base + lim; ++i) {
-        float gr = maximize ? -g[i] : g[i];
+        float gr = load_grad1(g, i);
+        if (maximize) gr = -gr;
         float pr = p[i];
         if (adamw) pr *= wd_mul; else gr += weight_decay * pr;
         float mr = beta1 * m[i] + one_minus_beta1 * gr;
@@ -210,8 +257,9 @@ __global__ void gather_rows_kernel(const float* __restrict__ src,
 // ---------------------------------------------------------------- Adagrad
 // g' = (max? -g : g) + wd*p ; sum += g'^2 ; p -= clr * g'/(sqrt(sum)+eps)
 // (clr = lr / (1 + (step-1)*lr_decay), host-computed)
+template <typename GT>
 __global__ void fused_adagrad_kernel(float* __restrict__ p,
-                                     const float* __restrict__ g,
+                                     const GT* __restrict__ g,
                                      float* __restrict__ sum, long n,
                                      float clr, float eps,
                                      float weight_decay, int maximize) {
@@ -220,10 +268,10 @@ __global__ void fused_adagrad_kernel(float* __restrict__ p,
        base < n; base += stride) {
     if (base + 3 < n) {
       float4 pv = *reinterpret_cast<float4*>(p + base);
-      float4 gv = *reinterpret_cast<const float4*>(g + base);
       float4 sv = *reinterpret_cast<float4*>(sum + base);
       float pr[4] = {pv.x, pv.y, pv.z, pv.w};
-      float gr[4] = {gv.x, gv.y, gv.z, gv.w};
+      float gr[4];
+      load_grad4(g, base, gr);
       float sr[4] = {sv.x, sv.y, sv.z, sv.w};
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -238,7 +286,8 @@ __global__ void fused_adagrad_kernel(float* __restrict__ p,
           make_float4(pr[0], pr[1], pr[2], pr[3]);
     } else {
       for (long i = base; i < n; ++i) {
-        float d = maximize ? -g[i] : g[i];
+        float d = load_grad1(g, i);
+        if (maximize) d = -d;
         d += weight_decay * p[i];
         sum[i] += d * d;
         p[i] -= clr * d / (sqrtf(sum[i]) + eps);

@@ -396,6 +396,30 @@ def apply_flat(cls_name: str, param: torch.Tensor, grad: torch.Tensor,
     apply_dense(cls_name, [param], [grad], [state], hyper)
 
 
+def apply_flat_shard(cls_name: str, param_shard: torch.Tensor,
+                     grad_shard: torch.Tensor, state: dict, hyper: dict):
+    """Update of the bucket shard this rank owns (sharded dense schedule).
+    `grad_shard` is the reduce-scattered shard: fp32, or the bf16 wire of the
+    cast compressors, which the gfx950 kernels consume directly
+    (ops.api.fused_apply_wire). Anything without a wire kernel, and the CPU,
+    widens the gradient (exactly) and takes the ordinary path."""
+    if grad_shard.dtype == torch.float32:
+        apply_flat(cls_name, param_shard, grad_shard, state, hyper)
+        return
+    if grad_shard.dtype == torch.bfloat16 and param_shard.is_cuda:
+        from autodist_amd.ops import api as ops_api
+        if ops_api.fused_apply_wire(cls_name, param_shard, grad_shard, state,
+                                    hyper):
+            return
+        if param_shard.data_ptr() % 16 or not param_shard.is_contiguous():
+            # not a layout the engine produces; the fp32 kernels read
+            # 16 B/lane too, so this goes to the torch composite
+            _APPLY[cls_name]([param_shard], [grad_shard.float()], [state],
+                             hyper)
+            return
+    apply_dense(cls_name, [param_shard], [grad_shard.float()], [state], hyper)
+
+
 # -- sparse (row-wise) applies: the SparseApply* table ----------------------
 
 def apply_sparse_rows(cls_name: str, param: torch.Tensor, rows: torch.Tensor,

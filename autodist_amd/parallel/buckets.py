@@ -12,10 +12,32 @@ sized for the xGMI mesh (7 p2p links x ~153 GB/s per GPU).
 from typing import Dict, List, Optional
 
 import torch
+import torch.distributed as dist
 
 from autodist_amd.const import DEFAULT_BUCKET_BYTES, DEFAULT_FIRST_BUCKET_BYTES
 from autodist_amd.parallel.compressor import Compressor
 from autodist_amd.utils import logging
+
+
+# A sharded bucket's shards start on multiples of this many elements, so
+# every shard is 16-byte aligned in fp32 and in the bf16 wire alike.
+SHARD_ALIGN_ELEMS = 8
+
+
+def sharded_layout(numel: int, world_size: int):
+    """(padded length, shard length L) of a sharded bucket holding `numel`
+    elements: the length is padded up to a multiple of world_size * 8, rank r
+    owns [r*L, (r+1)*L). Shards may cut through variables (every supported
+    optimizer is elementwise); the pad belongs to no parameter."""
+    quantum = world_size * SHARD_ALIGN_ELEMS
+    padded = max(1, -(-numel // quantum)) * quantum
+    return padded, padded // world_size
+
+
+def shard_bounds(numel: int, world_size: int, rank: int):
+    """[lo, hi) of the shard `rank` owns in a sharded bucket."""
+    _, shard_len = sharded_layout(numel, world_size)
+    return rank * shard_len, (rank + 1) * shard_len
 
 
 class Bucket:
@@ -24,11 +46,27 @@ class Bucket:
 
     Flattening params too means the whole bucket's optimizer update is ONE
     elementwise HIP kernel over contiguous HBM3E buffers — no multi-tensor
-    metadata, perfectly coalesced 16 B/lane access."""
+    metadata, perfectly coalesced 16 B/lane access.
+
+    schedule="sharded": instead of all-reduce + full update on every rank,
+    the gradients are reduce-scattered, each rank updates only the shard it
+    owns (optimizer state exists for that shard alone) and the parameters
+    are all-gathered. The flats are padded so shards are equal and aligned
+    (sharded_layout). After step(), .grad of a member holds this rank's
+    scaled LOCAL gradient, not the average."""
 
     def __init__(self, bucket_id: int, dtype: torch.dtype, device: torch.device,
-                 compressor: Compressor, cls_name: str = "", hyper: dict = None):
+                 compressor: Compressor, cls_name: str = "", hyper: dict = None,
+                 schedule: str = "allreduce", world_size: int = 1,
+                 rank: int = 0):
         self.id = bucket_id
+        self.schedule = schedule
+        self.world_size = world_size
+        self.rank = rank
+        self.padded_numel = 0             # == numel unless sharded
+        self.grad_shard: Optional[torch.Tensor] = None  # reduced shard
+        self.gather_event: Optional[torch.cuda.Event] = None
+        self._gather_clone = False        # backend rejected aliasing gather
         self.dtype = dtype
         self.device = device
         self.compressor = compressor
@@ -59,9 +97,16 @@ class Bucket:
     def allocate(self):
         """Allocate flat buffers; repoint every member's .data and .grad at
         views of them (values preserved)."""
-        self.flat = torch.zeros(self.numel, dtype=self.dtype, device=self.device)
-        self.flat_param = torch.empty(self.numel, dtype=self.dtype,
+        self.padded_numel = self.numel
+        if self.sharded:
+            self.padded_numel, _ = sharded_layout(self.numel, self.world_size)
+        self.flat = torch.zeros(self.padded_numel, dtype=self.dtype,
+                                device=self.device)
+        self.flat_param = torch.empty(self.padded_numel, dtype=self.dtype,
                                       device=self.device)
+        if self.padded_numel > self.numel:
+            # zero pad in both flats: it belongs to no parameter
+            self.flat_param[self.numel:].zero_()
         with torch.no_grad():
             for p, off, shape in zip(self.params, self.offsets, self.shapes):
                 n = p.numel()
@@ -72,6 +117,43 @@ class Bucket:
     @property
     def nbytes(self) -> int:
         return self.numel * self.flat.element_size() if self.flat is not None else 0
+
+    # -- sharded schedule layout -------------------------------------------
+    @property
+    def sharded(self) -> bool:
+        return self.schedule == "sharded"
+
+    @property
+    def shard_len(self) -> int:
+        return self.padded_numel // self.world_size if self.sharded \
+            else self.padded_numel
+
+    @property
+    def shard_range(self):
+        """[lo, hi) of the flats this rank updates (everything unless
+        sharded)."""
+        if not self.sharded:
+            return 0, self.padded_numel
+        return self.rank * self.shard_len, (self.rank + 1) * self.shard_len
+
+    def param_shard(self) -> torch.Tensor:
+        lo, hi = self.shard_range
+        return self.flat_param[lo:hi]
+
+    @property
+    def reduce_scatter_nbytes(self) -> int:
+        """Bytes this rank feeds one reduce-scatter (wire dtype)."""
+        if self.flat is None:
+            return 0
+        wire = self.compressor.wire_dtype or self.dtype
+        return self.padded_numel * torch.empty((), dtype=wire).element_size()
+
+    @property
+    def allgather_nbytes(self) -> int:
+        """Bytes one parameter all-gather assembles on this rank."""
+        if self.flat_param is None:
+            return 0
+        return self.padded_numel * self.flat_param.element_size()
 
     def ensure_views(self):
         """Re-install flat-buffer grad views if user code detached them.
@@ -98,6 +180,8 @@ class Bucket:
         self._handle = None
         self._issued = False
         self.done_event = None
+        self.grad_shard = None
+        self.gather_event = None
 
     def zero_(self):
         self.flat.zero_()
@@ -133,9 +217,58 @@ class Bucket:
             self._reduce(engine)
 
     def _reduce(self, engine):
+        if self.sharded:
+            self._handle = self.compressor.reduce_scatter(
+                self.flat, self.world_size, group=engine.process_group,
+                async_op=True, scale=engine.grad_scale())
+            return
         self._handle = self.compressor.reduce(
             self.flat, group=engine.process_group, async_op=True,
             scale=engine.grad_scale())
+
+    def _finalize_reduce(self):
+        if self.sharded:
+            self.grad_shard = self.compressor.finalize_shard(self._handle)
+        else:
+            self.compressor.finalize(self.flat, self._handle)
+
+    def reduced_grad_shard(self) -> torch.Tensor:
+        """The gradient the shard update consumes: the reduce-scattered
+        shard (wire dtype), or the whole flat when no collective ran."""
+        if self.grad_shard is not None:
+            return self.grad_shard
+        lo, hi = self.shard_range
+        return self.flat[lo:hi]
+
+    def gather_params(self, engine):
+        """All-gather the updated shards into flat_param on the comm stream
+        (after this bucket's apply); records gather_event for step()."""
+        shard = self.param_shard()
+        if engine.device.type == "cuda":
+            ev = torch.cuda.Event()
+            ev.record()  # the shard update, on the compute stream
+            engine.comm_stream.wait_event(ev)
+            with torch.cuda.stream(engine.comm_stream):
+                self._all_gather(shard, engine.process_group)
+            self.gather_event = torch.cuda.Event()
+            self.gather_event.record(engine.comm_stream)
+        else:
+            self._all_gather(shard, engine.process_group)
+
+    def _all_gather(self, shard, group):
+        # the input aliases its own slot of the output (in-place all-gather)
+        if not self._gather_clone:
+            try:
+                dist.all_gather_into_tensor(self.flat_param, shard,
+                                            group=group)
+                return
+            except (RuntimeError, ValueError) as exc:
+                logging.info("bucket %d: backend rejected the in-place "
+                             "all-gather (%s); gathering from a copy",
+                             self.id, exc)
+                self._gather_clone = True
+        dist.all_gather_into_tensor(self.flat_param, shard.clone(),
+                                    group=group)
 
     def finalize(self, engine):
         """Make the compute stream depend on this bucket's reduced result."""
@@ -143,7 +276,7 @@ class Bucket:
             return
         if engine.device.type == "cuda":
             with torch.cuda.stream(engine.comm_stream):
-                self.compressor.finalize(self.flat, self._handle)
+                self._finalize_reduce()
             self.done_event = torch.cuda.Event(
                 enable_timing=engine.comm_sampling)
             self.done_event.record(engine.comm_stream)
@@ -153,21 +286,22 @@ class Bucket:
                                           self.done_event)
                 self._t0 = None
         else:
-            self.compressor.finalize(self.flat, self._handle)
+            self._finalize_reduce()
 
 
 def build_buckets(items, device: torch.device,
                   bucket_bytes: int = DEFAULT_BUCKET_BYTES,
-                  first_bucket_bytes: int = DEFAULT_FIRST_BUCKET_BYTES
-                  ) -> List[Bucket]:
-    """Group (param, group_id, compressor_type, cls_name, hyper, hyper_key)
-    tuples into Buckets.
+                  first_bucket_bytes: int = DEFAULT_FIRST_BUCKET_BYTES,
+                  world_size: int = 1, rank: int = 0) -> List[Bucket]:
+    """Group (param, group_id, compressor_type, cls_name, hyper, hyper_key
+    [, schedule]) tuples into Buckets; schedule defaults to "allreduce".
 
     Keeps the strategy's group ids (one ScopedAllocator-group == >=1 buckets),
     splitting any group larger than bucket_bytes so collectives overlap with
     backward instead of waiting for one giant buffer. Buckets are homogeneous
-    in (dtype, optimizer class, hyperparams, compressor) so the whole bucket
-    updates with one fused kernel and one compressor instance.
+    in (dtype, optimizer class, hyperparams, compressor, schedule) so the
+    whole bucket updates with one fused kernel, one compressor instance and
+    one collective schedule. world_size/rank fix a sharded bucket's layout.
 
     Bucket order follows REVERSED registration order within each group, since
     autograd produces gradients roughly in reverse forward order — the first
@@ -176,16 +310,19 @@ def build_buckets(items, device: torch.device,
     in backward instead of waiting for a full-size buffer.
     """
     by_group: Dict[tuple, list] = {}
-    for param, group_id, comp_type, cls_name, hyper, hyper_key in items:
-        key = (group_id, param.dtype, cls_name, hyper_key, comp_type)
+    for item in items:
+        param, group_id, comp_type, cls_name, hyper, hyper_key = item[:6]
+        schedule = item[6] if len(item) > 6 else "allreduce"
+        key = (group_id, param.dtype, cls_name, hyper_key, comp_type,
+               schedule)
         by_group.setdefault(key, []).append((param, comp_type, hyper))
     buckets: List[Bucket] = []
     # sort key stringifies the hyper tuple: values of mixed types (None vs
     # bool from torch param-group internals) are not mutually orderable
-    for (group_id, dtype, cls_name, _, comp_type), members in sorted(
+    for (group_id, dtype, cls_name, _, comp_type, schedule), members in sorted(
             by_group.items(),
             key=lambda kv: (kv[0][0], kv[0][2], repr(kv[0][3]),
-                            repr(kv[0][4]))):
+                            repr(kv[0][4]), kv[0][5])):
         members = list(reversed(members))
         current = None
         cap = 0
@@ -195,7 +332,9 @@ def build_buckets(items, device: torch.device,
                 cap = first_bucket_bytes if not buckets else bucket_bytes
                 comp = Compressor.create(comp_type, f"bucket{len(buckets)}")
                 current = Bucket(len(buckets), dtype, device, comp,
-                                 cls_name=cls_name, hyper=hyper)
+                                 cls_name=cls_name, hyper=hyper,
+                                 schedule=schedule, world_size=world_size,
+                                 rank=rank)
                 buckets.append(current)
             current.add(param)
         logging.debug("group %s -> %d bucket(s)", group_id, len(buckets))

@@ -52,9 +52,53 @@ class Compressor:
         if handle is not None:
             handle.wait()
 
+    # -- sharded schedule: reduce-scatter instead of all-reduce ------------
+    def reduce_scatter(self, flat: torch.Tensor, world: int, group=None,
+                       async_op: bool = False, scale: float = 1.0):
+        """Same front half as `reduce` (scale / compress over the whole
+        flat), then reduce-scatter: rank r receives the sum of elements
+        [r*L, (r+1)*L), L = numel/world, in a persistent shard buffer kept
+        in the WIRE dtype (nothing is cast back). Returns a handle for
+        `finalize_shard`."""
+        raise NotImplementedError(
+            f"{type(self).__name__} has no reduce-scatter form")
+
+    def finalize_shard(self, handle) -> torch.Tensor:
+        """Complete an async reduce_scatter; returns the reduced shard."""
+        h, shard = handle
+        if h is not None:
+            h.wait()
+        return shard
+
+    def _shard_buf(self, src: torch.Tensor, world: int) -> torch.Tensor:
+        n = src.numel() // world
+        buf = getattr(self, "_shard", None)
+        if buf is None or buf.numel() != n or buf.dtype != src.dtype \
+                or buf.device != src.device:
+            buf = self._shard = torch.empty(n, dtype=src.dtype,
+                                            device=src.device)
+        return buf
+
+    def _scatter(self, src, world, group, async_op):
+        shard = self._shard_buf(src, world)
+        handle = dist.reduce_scatter_tensor(shard, src, op=dist.ReduceOp.SUM,
+                                            group=group, async_op=async_op)
+        return (handle, shard)
+
+    @property
+    def wire_dtype(self) -> Optional[torch.dtype]:
+        """Element type on the wire; None = the bucket's own dtype."""
+        return None
+
 
 class NoneCompressor(Compressor):
     """Pass-through all-reduce (reference compressor.py:146-166)."""
+
+    def reduce_scatter(self, flat, world, group=None, async_op=False,
+                       scale=1.0):
+        if scale != 1.0:
+            flat.mul_(scale)
+        return self._scatter(flat, world, group, async_op)
 
     def reduce(self, flat, group=None, async_op=False, scale=1.0):
         if scale != 1.0:
@@ -97,6 +141,17 @@ class HorovodCompressor(Compressor):
             h.wait()
         ops_api.cast_back_f32(wire, flat)
 
+    @property
+    def wire_dtype(self):
+        return self.WIRE_DTYPE
+
+    def reduce_scatter(self, flat, world, group=None, async_op=False,
+                       scale=1.0):
+        from autodist_amd.ops import api as ops_api
+        wire = self._wire_buf(flat)
+        ops_api.scale_cast_bf16(flat, wire, scale)
+        return self._scatter(wire, world, group, async_op)
+
 
 class HorovodCompressorEF(HorovodCompressor):
     """Cast compression with error feedback (reference compressor.py:204-205):
@@ -116,3 +171,12 @@ class HorovodCompressorEF(HorovodCompressor):
         handle = dist.all_reduce(wire, op=dist.ReduceOp.SUM, group=group,
                                  async_op=async_op)
         return (handle, wire)
+
+    def reduce_scatter(self, flat, world, group=None, async_op=False,
+                       scale=1.0):
+        from autodist_amd.ops import api as ops_api
+        if self._error is None:
+            self._error = torch.zeros_like(flat)
+        wire = self._wire_buf(flat)
+        ops_api.ef_compress(flat, self._error, wire, scale)
+        return self._scatter(wire, world, group, async_op)

@@ -10,7 +10,10 @@ directly:
   * AllReduce vars   -> flat gradient buckets + RCCL all-reduce on a comm
                         HIP stream, issued from post-accumulate-grad hooks so
                         collectives overlap backward
-                        (reference: all_reduce_synchronizer.py:102-130).
+                        (reference: all_reduce_synchronizer.py:102-130); with
+                        schedule="sharded": reduce-scatter, each rank updates
+                        the 1/world bucket shard it owns with shard-local
+                        optimizer state, then the parameters are all-gathered.
   * PS vars          -> shard owners hold a master copy + shard-local
                         optimizer state; reduce->apply->broadcast pipelined on
                         the comm stream with optional bounded staleness
@@ -58,6 +61,7 @@ class ShardPlan:
     staleness: int = 0
     local_replication: bool = False
     sparse_routing: str = "replicated"   # PS only: "replicated" | "owner"
+    schedule: str = "allreduce"          # AR only: "allreduce" | "sharded"
     # runtime state
     state: Optional[dict] = None           # optimizer state (applier ranks)
     master: Optional[torch.Tensor] = None  # PS master copy (owner)
@@ -192,6 +196,9 @@ class DistributedEngine:
         # step's sparse sync (padding excluded); see stats()
         self._sparse_rows_received = 0
         self._fallback_user_opt = False
+        # sharded buckets run as "allreduce" because the user's own
+        # optimizer.step() applies the update (see _build_buckets_and_hooks)
+        self._sharded_downgraded = False
         self._setup_done = False
         self._accumulating = False
         # one SHARED live hyperparam dict per optimizer param_group; plans,
@@ -412,7 +419,8 @@ class DistributedEngine:
         if node.all_reduce_synchronizer is not None:
             s = node.all_reduce_synchronizer
             return ShardPlan(name=node.var_name, kind="allreduce", slice=sl,
-                             group=s.group, compressor=s.compressor)
+                             group=s.group, compressor=s.compressor,
+                             schedule=s.schedule)
         if node.ps_synchronizer is not None:
             s = node.ps_synchronizer
             return ShardPlan(name=node.var_name, kind="ps", slice=sl,
@@ -473,13 +481,25 @@ class DistributedEngine:
                 continue
             if whole and sh0.kind == "allreduce":
                 plan.bucketed = True
+                schedule = sh0.schedule
+                if schedule == "sharded" and self._fallback_user_opt:
+                    # the user's optimizer.step() needs the averaged gradient
+                    # of every element on every rank
+                    if not self._sharded_downgraded:
+                        logging.warning(
+                            "schedule='sharded' needs an optimizer class the "
+                            "engine applies itself; %s is not one: running "
+                            "those buckets with schedule='allreduce'",
+                            plan.cls_name)
+                    self._sharded_downgraded = True
+                    schedule = sh0.schedule = "allreduce"
                 # group_index in the key keeps buckets homogeneous in LIVE
                 # param_group (two groups with equal initial hyper may
                 # diverge later under a scheduler)
                 bucket_items.append((plan.param, sh0.group, sh0.compressor,
                                      plan.cls_name, plan.hyper,
                                      (plan.group_index,
-                                      _hyper_key(plan.hyper))))
+                                      _hyper_key(plan.hyper)), schedule))
             elif sh0.kind == "allreduce":
                 # partitioned AR: per-shard direct reducers
                 for sh in plan.shards:
@@ -503,7 +523,10 @@ class DistributedEngine:
         from autodist_amd.parallel.ps_synchronizer import PSSynchronizer
         self.ps_groups = PSSynchronizer.build_groups(self, ps_items)
         # PS/partitioned params keep ordinary grads; bucketed params get views
-        self.buckets = build_buckets(bucket_items, self.device, self.bucket_bytes)
+        self.buckets = build_buckets(bucket_items, self.device,
+                                     self.bucket_bytes,
+                                     world_size=self.world_size,
+                                     rank=self.rank)
         # deterministic cross-rank collective keys (reference
         # collective_key.py:43-70): instance key = md5 of member var names,
         # group key = the replica device set; engine.step() flushes unissued
@@ -665,6 +688,12 @@ class DistributedEngine:
             orig()
         else:
             self._apply_dense_updates()
+        #    sharded buckets: the parameter all-gathers run on the comm
+        #    stream; the next forward must see them
+        if self.device.type == "cuda":
+            for b in self.buckets:
+                if b.gather_event is not None:
+                    torch.cuda.current_stream().wait_event(b.gather_event)
         # 6) consume due PS rounds (staleness bound)
         for grp in self.ps_groups:
             grp.consume_due(self)
@@ -683,9 +712,24 @@ class DistributedEngine:
 
     # -- dense AR apply ----------------------------------------------------
     def _apply_dense_updates(self):
-        # bucketed params: one fused flat update per bucket
-        for b in self.buckets:
+        # bucketed params: one fused flat update per bucket. Instance-key
+        # order: sharded buckets enqueue a collective each, and every rank
+        # must enqueue the same sequence.
+        for b in sorted(self.buckets, key=lambda b: b.instance_key):
             if not b.params:
+                continue
+            if b.sharded:
+                # update only the shard this rank owns, straight from the
+                # reduce-scattered (wire dtype) gradient shard; bucket i's
+                # all-gather overlaps bucket i+1's update
+                shard = b.param_shard()
+                if not b.state:
+                    b.state = apply_mod.make_state(b.cls_name, shard, b.hyper)
+                apply_mod.apply_flat_shard(b.cls_name, shard,
+                                           b.reduced_grad_shard(), b.state,
+                                           b.hyper)
+                if self.collectives_active:
+                    b.gather_params(self)
                 continue
             if not b.state:
                 b.state = apply_mod.make_state(b.cls_name, b.flat_param, b.hyper)
@@ -886,6 +930,7 @@ class DistributedEngine:
         reference's SaveSliceInfo reassembly (partitioner.py:292-346).
         """
         out: Dict[str, dict] = {}
+        gathered: Dict[tuple, torch.Tensor] = {}  # sharded-bucket state
         param_to_bucket = {}
         for b in self.buckets:
             for p, off in zip(b.params, b.offsets):
@@ -905,8 +950,19 @@ class DistributedEngine:
                     t = b.state[k]
                     if t.dim() == 0:  # shared step counter
                         state[k] = t.clone()
-                    else:
-                        state[k] = t[off:off + n].view(plan.param.shape).clone()
+                        continue
+                    if b.sharded and self.collectives_active:
+                        # shard-local state: assemble the bucket's full
+                        # tensor once, slice it per variable
+                        if (b.id, k) not in gathered:
+                            full = torch.empty(b.padded_numel, dtype=t.dtype,
+                                               device=t.device)
+                            dist.all_gather_into_tensor(
+                                full, t.contiguous(),
+                                group=self.process_group)
+                            gathered[(b.id, k)] = full
+                        t = gathered[(b.id, k)]
+                    state[k] = t[off:off + n].view(plan.param.shape).clone()
             elif (plan.shards[0].kind == "local"
                   and getattr(plan.param, "_autodist_shard_range", None)
                   and self.world_size > 1):
@@ -1005,8 +1061,10 @@ class DistributedEngine:
             if plan.bucketed:
                 b, off = param_to_bucket[id(plan.param)]
                 n = plan.param.numel()
+                lo, hi = b.shard_range
                 if not b.state:
-                    b.state = apply_mod.make_state(b.cls_name, b.flat_param,
+                    b.state = apply_mod.make_state(b.cls_name,
+                                                   b.flat_param[lo:hi],
                                                    b.hyper)
                 for k in keys:
                     if k not in state:
@@ -1015,6 +1073,14 @@ class DistributedEngine:
                     if k == "step":
                         b.state[k] = src.to(b.state.get(k, src).dtype) \
                             if "step" in b.state else src.clone()
+                    elif b.sharded:
+                        # write only what falls into this rank's shard
+                        if k not in b.state:
+                            b.state[k] = torch.zeros_like(b.flat[lo:hi])
+                        a, z = max(off, lo), min(off + n, hi)
+                        if a < z:
+                            b.state[k][a - lo:z - lo].copy_(
+                                src.reshape(-1)[a - off:z - off])
                     else:
                         if k not in b.state:
                             b.state[k] = torch.zeros_like(b.flat)
@@ -1075,7 +1141,13 @@ class DistributedEngine:
     def stats(self) -> dict:
         """Per-step synchronization accounting (observability — the
         reference had logging only, §5.5)."""
-        ar_bytes = sum(b.nbytes for b in self.buckets)
+        ar_bytes = sum(b.nbytes for b in self.buckets if not b.sharded)
+        sharded = [b for b in self.buckets if b.sharded]
+        # per-element optimizer state this rank holds for bucketed variables
+        # (1/world of it under the sharded schedule)
+        state_bytes = sum(t.numel() * t.element_size()
+                          for b in self.buckets for t in b.state.values()
+                          if isinstance(t, torch.Tensor) and t.dim() > 0)
         ps_bytes = 0
         shard_reduce_bytes = 0
         n_ps_shards = 0
@@ -1095,6 +1167,13 @@ class DistributedEngine:
             "world_size": self.world_size,
             "n_buckets": len(self.buckets),
             "allreduce_bytes_per_step": ar_bytes,
+            "sharded_buckets": len(sharded),
+            "sharded_downgraded": self._sharded_downgraded,
+            "reduce_scatter_bytes_per_step": sum(
+                b.reduce_scatter_nbytes for b in sharded),
+            "allgather_bytes_per_step": sum(
+                b.allgather_nbytes for b in sharded),
+            "dense_optimizer_state_bytes_local": state_bytes,
             "ps_shards": n_ps_shards,
             "ps_owner_groups": len(self.ps_groups),
             "ps_collectives_per_step": 2 * len(self.ps_groups),

@@ -34,6 +34,7 @@ class CompressorType(enum.IntEnum):
 
 
 SPARSE_ROUTING_MODES = ("replicated", "owner")
+DENSE_AR_SCHEDULES = ("allreduce", "sharded")
 
 
 @dataclasses.dataclass
@@ -73,16 +74,35 @@ class AllReduceSynchronizer:
     spec: AllReduceSpec = AllReduceSpec.AUTO
     compressor: CompressorType = CompressorType.NoneCompressor
     group: int = 0                    # bucket/fusion group id
+    # Addition over the reference proto: how a dense bucket is synchronized
+    # and updated. "allreduce" = all-reduce the bucket, every rank runs the
+    # full update with full optimizer state; "sharded" = reduce-scatter, each
+    # rank updates the 1/world shard it owns with shard-local state, then
+    # all-gather the parameters. Sparse variables ignore it.
+    schedule: str = "allreduce"
+
+    def __post_init__(self):
+        if self.schedule not in DENSE_AR_SCHEDULES:
+            raise ValueError(
+                f"schedule must be one of {DENSE_AR_SCHEDULES}, "
+                f"got {self.schedule!r}")
+        if (self.schedule == "sharded"
+                and self.compressor == CompressorType.PowerSGDCompressor):
+            # its low-rank factors are not elementwise-shardable
+            raise ValueError(
+                "schedule='sharded' cannot be combined with "
+                "PowerSGDCompressor")
 
     def to_dict(self):
         return {"spec": int(self.spec), "compressor": int(self.compressor),
-                "group": self.group}
+                "group": self.group, "schedule": self.schedule}
 
     @classmethod
     def from_dict(cls, d):
         return cls(spec=AllReduceSpec(d.get("spec", 0)),
                    compressor=CompressorType(d.get("compressor", 0)),
-                   group=d.get("group", 0))
+                   group=d.get("group", 0),
+                   schedule=d.get("schedule", "allreduce"))
 
 
 @dataclasses.dataclass

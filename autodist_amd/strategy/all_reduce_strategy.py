@@ -14,7 +14,8 @@ DEFAULT_BUCKET_BYTES so a group never exceeds what overlaps well on a
 from autodist_amd.proto.strategy_ir import (AllReduceSpec,
                                             AllReduceSynchronizer,
                                             CompressorType, Node)
-from autodist_amd.strategy.base import Strategy, StrategyBuilder
+from autodist_amd.strategy.base import (Strategy, StrategyBuilder,
+                                        resolve_dense_schedule)
 
 
 class AllReduce(StrategyBuilder):
@@ -22,12 +23,15 @@ class AllReduce(StrategyBuilder):
     all_reduce_strategy.py:47-69)."""
 
     def __init__(self, chunk_size=128, all_reduce_spec="RCCL",
-                 compressor="NoneCompressor"):
+                 compressor="NoneCompressor", schedule=None):
         if chunk_size < 1:
             raise ValueError("chunk_size must be >= 1")
         self.chunk_size = chunk_size
         self.all_reduce_spec = all_reduce_spec
         self.compressor = compressor
+        # "allreduce" | "sharded" (reduce-scatter, shard-local update,
+        # all-gather); None = the AUTODIST_DENSE_AR_SCHEDULE flag
+        self.schedule = resolve_dense_schedule(schedule, compressor)
 
     def build(self, graph_item, resource_spec) -> Strategy:
         strategy = Strategy()
@@ -45,5 +49,6 @@ class AllReduce(StrategyBuilder):
         compressor = CompressorType[self.compressor]
         return [
             Node(var_name=name, all_reduce_synchronizer=AllReduceSynchronizer(
-                spec=spec, compressor=compressor, group=i // self.chunk_size))
+                spec=spec, compressor=compressor, group=i // self.chunk_size,
+                schedule=self.schedule))
             for i, name in enumerate(var_names)]

@@ -21,7 +21,9 @@ class AutoStrategy(StrategyBuilder):
 
     def __init__(self, candidates=None):
         self._candidates = candidates or [
-            AllReduce(), PartitionedAR(), Parallax(),
+            # the cost model does not rank the sharded dense schedule yet
+            AllReduce(schedule="allreduce"), PartitionedAR(),
+            Parallax(schedule="allreduce"),
             PSLoadBalancing(), PartitionedPS(),
         ]
 

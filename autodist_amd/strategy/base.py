@@ -6,7 +6,8 @@ import os
 from datetime import datetime
 
 from autodist_amd.const import DEFAULT_SERIALIZATION_DIR, ENV
-from autodist_amd.proto.strategy_ir import (SPARSE_ROUTING_MODES, GraphConfig,
+from autodist_amd.proto.strategy_ir import (DENSE_AR_SCHEDULES,
+                                            SPARSE_ROUTING_MODES, GraphConfig,
                                             StrategyProto)
 from autodist_amd.utils import logging
 
@@ -81,6 +82,23 @@ def resolve_sparse_routing(value=None) -> str:
     if value not in SPARSE_ROUTING_MODES:
         raise ValueError(f"sparse_routing must be one of "
                          f"{SPARSE_ROUTING_MODES}, got {value!r}")
+    return value
+
+
+def resolve_dense_schedule(value=None, compressor="NoneCompressor") -> str:
+    """AllReduce/Parallax builders' `schedule` keyword: None reads the
+    AUTODIST_DENSE_AR_SCHEDULE flag (default "allreduce"), so benchmarks and
+    examples can exercise the sharded dense schedule unedited. Raises at
+    build time for the combinations the IR rejects."""
+    if value is None:
+        value = ENV.AUTODIST_DENSE_AR_SCHEDULE.val
+    if value not in DENSE_AR_SCHEDULES:
+        raise ValueError(f"schedule must be one of {DENSE_AR_SCHEDULES}, "
+                         f"got {value!r}")
+    if value == "sharded" and compressor == "PowerSGDCompressor":
+        raise ValueError("schedule='sharded' cannot be combined with "
+                         "PowerSGDCompressor (its low-rank factors are not "
+                         "elementwise-shardable)")
     return value
 
 

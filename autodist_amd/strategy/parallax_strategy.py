@@ -12,7 +12,7 @@ from autodist_amd.proto.strategy_ir import (AllReduceSpec,
                                             AllReduceSynchronizer,
                                             CompressorType, Node,
                                             PSSynchronizer)
-from autodist_amd.strategy.base import Strategy
+from autodist_amd.strategy.base import Strategy, resolve_dense_schedule
 from autodist_amd.strategy.ps_lb_strategy import PSLoadBalancing, byte_size_load_fn
 
 
@@ -21,12 +21,14 @@ class Parallax(PSLoadBalancing):
 
     def __init__(self, chunk_size=128, local_proxy_variable=False, sync=True,
                  staleness=0, all_reduce_spec="RCCL", compressor="NoneCompressor",
-                 sparse_routing=None):
+                 sparse_routing=None, schedule=None):
         super().__init__(local_proxy_variable, sync, staleness,
                          sparse_routing=sparse_routing)
         self.chunk_size = chunk_size
         self.all_reduce_spec = all_reduce_spec
         self.compressor = compressor
+        # dense variables' schedule, as in AllReduce
+        self.schedule = resolve_dense_schedule(schedule, compressor)
 
     def build(self, graph_item, resource_spec) -> Strategy:
         strategy = Strategy()
@@ -55,7 +57,8 @@ class Parallax(PSLoadBalancing):
                     var_name=v.name,
                     all_reduce_synchronizer=AllReduceSynchronizer(
                         spec=spec, compressor=compressor,
-                        group=dense_idx // self.chunk_size)))
+                        group=dense_idx // self.chunk_size,
+                        schedule=self.schedule)))
                 dense_idx += 1
         strategy.node_config = configs
         return strategy
