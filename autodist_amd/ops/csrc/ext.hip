@@ -62,14 +62,31 @@ inline int bn_reduce_gm(const BNGeom& g) {
   return (int)gm;
 }
 
-std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
-                                        torch::Tensor bias,
-                                        torch::Tensor running_mean,
-                                        torch::Tensor running_var,
-                                        c10::optional<torch::Tensor> res,
-                                        double eps, double momentum,
-                                        bool relu,
-                                        c10::optional<torch::Tensor> ws) {
+template <typename T>
+T* bn_ptr(const torch::Tensor& t) {
+  return reinterpret_cast<T*>(t.data_ptr());
+}
+
+template <typename T, bool RELU, bool ADD, bool MASK>
+void bn_launch_fwd_apply(dim3 grid, hipStream_t st, const torch::Tensor& x,
+                         const torch::Tensor* res, torch::Tensor& y,
+                         unsigned char* mask, const float* scale,
+                         const float* shift, const BNGeom& g) {
+  hipLaunchKernelGGL((bn_fwd_apply_kernel<T, RELU, ADD, MASK>), grid,
+                     dim3(BLOCK_THREADS), 0, st, bn_ptr<const T>(x),
+                     ADD ? bn_ptr<const T>(*res) : (const T*)nullptr,
+                     bn_ptr<T>(y), mask, scale, shift, g.M, g.C);
+}
+
+// with_mask: also return the bit-packed ReLU mask of y ([M, C/8] uint8, see
+// bn_fwd_apply_kernel), which bn_bwd_mask takes in place of y.
+template <typename T>
+std::vector<torch::Tensor> bn_fwd_impl(
+    const torch::Tensor& x, const torch::Tensor& weight,
+    const torch::Tensor& bias, torch::Tensor& running_mean,
+    torch::Tensor& running_var, const c10::optional<torch::Tensor>& res,
+    double eps, double momentum, bool relu,
+    const c10::optional<torch::Tensor>& ws, bool with_mask) {
   // ws: persistent per-module workspace [2*BN_GM_MAX + 4, C] fp32:
   //   rows [0, GM)               partial sums (per reduce block)
   //   rows [BN_GM_MAX, BN_GM_MAX+GM) partial sumsq
@@ -77,9 +94,11 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
   //   rows 2*BN_GM_MAX + {2,3}: scale, shift
   // Everything in ws is dead once this call's apply kernel has run, so a
   // later call on the same module may overwrite it. save_mean / save_rstd
-  // are NOT in ws: autograd keeps them until backward, and a module called
-  // twice before backward (shared tower, micro-batches summed into one
-  // loss) would otherwise hand the first backward the second call's stats.
+  // and the mask are NOT in ws: autograd keeps them until backward, and a
+  // module called twice before backward (shared tower, micro-batches summed
+  // into one loss) would otherwise hand the first backward the second
+  // call's stats.
+  TORCH_CHECK(!with_mask || relu, "the mask is the ReLU mask: relu must be set");
   auto g = bn_geom(x);
   auto fopt = weight.options().dtype(torch::kFloat32);
   torch::Tensor w6 = ws.has_value() ? *ws
@@ -89,77 +108,99 @@ std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
   float* wp = w6.data_ptr<float>();
   float* partial_sum = wp;
   float* partial_sq = wp + (long)BN_GM_MAX * g.C;
-  // fresh allocation: saved for backward (one caching-allocator hit, no
-  // launch)
+  // fresh allocations: saved for backward (caching-allocator hits, no
+  // launch, no fill)
   auto stats = torch::empty({2, (long)g.C}, fopt);
   auto save_mean = stats[0];
   auto save_rstd = stats[1];
-  auto scale = w6[2 * BN_GM_MAX + 2];
-  auto shift = w6[2 * BN_GM_MAX + 3];
+  torch::Tensor mask;
+  if (with_mask)
+    mask = torch::empty({g.M, (long)(g.C / BN_VEC)},
+                        x.options().dtype(torch::kUInt8));
+  unsigned char* mp = with_mask ? mask.data_ptr<unsigned char>() : nullptr;
+  const float* scale = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
+  const float* shift = wp + (long)(2 * BN_GM_MAX + 3) * g.C;
   auto y = torch::empty_like(x);
-  dim3 block(BLOCK_THREADS);
   int gm = bn_reduce_gm(g);
   dim3 grid_r(gm, g.grid_c);
   dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
   auto st = cur_stream();
 
-#define BN_FWD_T(T, GET)                                                      \
-  {                                                                           \
-    hipLaunchKernelGGL((bn_fwd_reduce_kernel<T>), grid_r, block, 0, st,       \
-                       GET(x), partial_sum, partial_sq, g.M, g.C);            \
-    hipLaunchKernelGGL(bn_fwd_finalize_kernel,                                \
-                       dim3((g.C + FIN_CH - 1) / FIN_CH),                     \
-                       dim3(FIN_CH * FIN_LANES), 0, st, partial_sum,          \
-                       partial_sq, gm,                                        \
-                       weight.data_ptr<float>(),                              \
-                       bias.data_ptr<float>(), running_mean.data_ptr<float>(),\
-                       running_var.data_ptr<float>(),                         \
-                       save_mean.data_ptr<float>(),                           \
-                       save_rstd.data_ptr<float>(), scale.data_ptr<float>(),  \
-                       shift.data_ptr<float>(), g.M, g.C, (float)eps,         \
-                       (float)momentum);                                      \
-    if (res.has_value()) {                                                    \
-      if (relu)                                                               \
-        hipLaunchKernelGGL((bn_fwd_apply_kernel<T, true, true>), grid_a,      \
-                           block, 0, st, GET(x), GET(*res), GET(y),           \
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),  \
-                           g.M, g.C);                                         \
-      else                                                                    \
-        hipLaunchKernelGGL((bn_fwd_apply_kernel<T, false, true>), grid_a,     \
-                           block, 0, st, GET(x), GET(*res), GET(y),           \
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),  \
-                           g.M, g.C);                                         \
-    } else {                                                                  \
-      if (relu)                                                               \
-        hipLaunchKernelGGL((bn_fwd_apply_kernel<T, true, false>), grid_a,     \
-                           block, 0, st, GET(x), (const T*)nullptr, GET(y),   \
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),  \
-                           g.M, g.C);                                         \
-      else                                                                    \
-        hipLaunchKernelGGL((bn_fwd_apply_kernel<T, false, false>), grid_a,    \
-                           block, 0, st, GET(x), (const T*)nullptr, GET(y),   \
-                           scale.data_ptr<float>(), shift.data_ptr<float>(),  \
-                           g.M, g.C);                                         \
-    }                                                                         \
-  }
-
-#define GET_BF16(t) reinterpret_cast<__hip_bfloat16*>((t).data_ptr())
-#define GET_F32(t) (t).data_ptr<float>()
-  if (x.scalar_type() == torch::kBFloat16) {
-    BN_FWD_T(__hip_bfloat16, GET_BF16)
+  hipLaunchKernelGGL((bn_fwd_reduce_kernel<T>), grid_r, dim3(BLOCK_THREADS),
+                     0, st, bn_ptr<const T>(x), partial_sum, partial_sq, g.M,
+                     g.C);
+  hipLaunchKernelGGL(bn_fwd_finalize_kernel,
+                     dim3((g.C + FIN_CH - 1) / FIN_CH),
+                     dim3(FIN_CH * FIN_LANES), 0, st, partial_sum, partial_sq,
+                     gm, weight.data_ptr<float>(), bias.data_ptr<float>(),
+                     running_mean.data_ptr<float>(),
+                     running_var.data_ptr<float>(),
+                     save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
+                     const_cast<float*>(scale), const_cast<float*>(shift),
+                     g.M, g.C, (float)eps, (float)momentum);
+  const torch::Tensor* rp = res.has_value() ? &*res : nullptr;
+#define BN_FWD_APPLY(RELU, ADD, MASK)                                        \
+  bn_launch_fwd_apply<T, RELU, ADD, MASK>(grid_a, st, x, rp, y, mp, scale,  \
+                                          shift, g)
+  if (rp) {
+    if (with_mask) BN_FWD_APPLY(true, true, true);
+    else if (relu) BN_FWD_APPLY(true, true, false);
+    else BN_FWD_APPLY(false, true, false);
   } else {
-    TORCH_CHECK(x.scalar_type() == torch::kFloat32);
-    BN_FWD_T(float, GET_F32)
+    if (with_mask) BN_FWD_APPLY(true, false, true);
+    else if (relu) BN_FWD_APPLY(true, false, false);
+    else BN_FWD_APPLY(false, false, false);
   }
+#undef BN_FWD_APPLY
+  if (with_mask) return {y, save_mean, save_rstd, mask};
   return {y, save_mean, save_rstd};
 }
 
-std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
-                                  torch::Tensor y, torch::Tensor save_mean,
-                                  torch::Tensor save_rstd,
-                                  torch::Tensor weight, bool relu,
-                                  bool need_dres,
-                                  c10::optional<torch::Tensor> ws) {
+std::vector<torch::Tensor> bn_fwd_dispatch(
+    const torch::Tensor& x, const torch::Tensor& weight,
+    const torch::Tensor& bias, torch::Tensor& running_mean,
+    torch::Tensor& running_var, const c10::optional<torch::Tensor>& res,
+    double eps, double momentum, bool relu,
+    const c10::optional<torch::Tensor>& ws, bool with_mask) {
+  if (x.scalar_type() == torch::kBFloat16)
+    return bn_fwd_impl<__hip_bfloat16>(x, weight, bias, running_mean,
+                                       running_var, res, eps, momentum, relu,
+                                       ws, with_mask);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32);
+  return bn_fwd_impl<float>(x, weight, bias, running_mean, running_var, res,
+                            eps, momentum, relu, ws, with_mask);
+}
+
+std::vector<torch::Tensor> bn_fwd_train(torch::Tensor x, torch::Tensor weight,
+                                        torch::Tensor bias,
+                                        torch::Tensor running_mean,
+                                        torch::Tensor running_var,
+                                        c10::optional<torch::Tensor> res,
+                                        double eps, double momentum,
+                                        bool relu,
+                                        c10::optional<torch::Tensor> ws) {
+  return bn_fwd_dispatch(x, weight, bias, running_mean, running_var, res, eps,
+                         momentum, relu, ws, false);
+}
+
+// -> (y, save_mean, save_rstd, mask); relu must be true
+std::vector<torch::Tensor> bn_fwd_train_mask(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var,
+    c10::optional<torch::Tensor> res, double eps, double momentum, bool relu,
+    c10::optional<torch::Tensor> ws) {
+  return bn_fwd_dispatch(x, weight, bias, running_mean, running_var, res, eps,
+                         momentum, relu, ws, true);
+}
+
+// RELU: BN_RELU_NONE / BN_RELU_Y (yq is y, same dtype and layout as x) /
+// BN_RELU_MASK (yq is the forward's packed mask).
+template <typename T, int RELU>
+std::vector<torch::Tensor> bn_bwd_impl(
+    const torch::Tensor& x, const torch::Tensor& dy, const torch::Tensor& yq,
+    const torch::Tensor& save_mean, const torch::Tensor& save_rstd,
+    const torch::Tensor& weight, bool need_dres,
+    const c10::optional<torch::Tensor>& ws) {
   // ws rows: [0,GM) partial_dz, [BN_GM_MAX, BN_GM_MAX+GM) partial_dzxh,
   //          2*BN_GM_MAX + {0,1,2}: k1, k2, k3.
   auto g = bn_geom(x);
@@ -168,12 +209,23 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
       : torch::empty({2 * BN_GM_MAX + 3, (long)g.C}, fopt);
   TORCH_CHECK(w5.size(0) >= 2 * BN_GM_MAX + 3 && w5.size(1) == g.C &&
               w5.is_contiguous());
+  const T* yp = nullptr;
+  const unsigned char* mp = nullptr;
+  if (RELU == BN_RELU_MASK) {
+    TORCH_CHECK(yq.scalar_type() == torch::kUInt8 && yq.is_contiguous() &&
+                    yq.dim() == 2 && yq.size(0) == g.M &&
+                    yq.size(1) == g.C / BN_VEC && yq.device() == x.device(),
+                "mask must be the [M, C/8] uint8 tensor of bn_fwd_train_mask");
+    mp = yq.data_ptr<unsigned char>();
+  } else {
+    yp = bn_ptr<const T>(yq);
+  }
   float* wp = w5.data_ptr<float>();
   float* partial_dz = wp;
   float* partial_dzxh = wp + (long)BN_GM_MAX * g.C;
-  auto k1 = w5[2 * BN_GM_MAX + 0];
-  auto k2 = w5[2 * BN_GM_MAX + 1];
-  auto k3 = w5[2 * BN_GM_MAX + 2];
+  float* k1 = wp + (long)(2 * BN_GM_MAX + 0) * g.C;
+  float* k2 = wp + (long)(2 * BN_GM_MAX + 1) * g.C;
+  float* k3 = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
   // fresh allocations: returned to autograd as parameter gradients
   auto dweight = torch::empty({g.C}, fopt);
   auto dbias = torch::empty({g.C}, fopt);
@@ -185,72 +237,71 @@ std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
   dim3 grid_r(gm, g.grid_c);
   dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
   auto st = cur_stream();
+  const float* sm = save_mean.data_ptr<float>();
+  const float* sr = save_rstd.data_ptr<float>();
 
-#define BN_BWD_T(T, GET)                                                      \
-  {                                                                           \
-    if (relu)                                                                 \
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), grid_r, block, 0,   \
-                         st, GET(x), GET(dy), GET(y),                         \
-                         save_mean.data_ptr<float>(),                         \
-                         save_rstd.data_ptr<float>(),                         \
-                         partial_dz, partial_dzxh, g.M, g.C);                 \
-    else                                                                      \
-      hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false>), grid_r, block, 0,  \
-                         st, GET(x), GET(dy), GET(y),                         \
-                         save_mean.data_ptr<float>(),                         \
-                         save_rstd.data_ptr<float>(),                         \
-                         partial_dz, partial_dzxh, g.M, g.C);                 \
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel,                                \
-                       dim3((g.C + FIN_CH - 1) / FIN_CH),                     \
-                       dim3(FIN_CH * FIN_LANES), 0, st, partial_dz,           \
-                       partial_dzxh, gm,                                      \
-                       weight.data_ptr<float>(),                              \
-                       save_rstd.data_ptr<float>(), k1.data_ptr<float>(),     \
-                       k2.data_ptr<float>(), k3.data_ptr<float>(),            \
-                       dweight.data_ptr<float>(), dbias.data_ptr<float>(),    \
-                       g.M, g.C);                                             \
-    T* dres_p = need_dres ? GET(dres) : (T*)nullptr;                          \
-    if (relu) {                                                               \
-      if (need_dres)                                                          \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, true>), grid_a,      \
-                           block, 0, st, GET(x), GET(dy), GET(y),             \
-                           save_mean.data_ptr<float>(),                       \
-                           save_rstd.data_ptr<float>(), k1.data_ptr<float>(), \
-                           k2.data_ptr<float>(), k3.data_ptr<float>(),        \
-                           GET(dx), dres_p, g.M, g.C);                        \
-      else                                                                    \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, true, false>), grid_a,     \
-                           block, 0, st, GET(x), GET(dy), GET(y),             \
-                           save_mean.data_ptr<float>(),                       \
-                           save_rstd.data_ptr<float>(), k1.data_ptr<float>(), \
-                           k2.data_ptr<float>(), k3.data_ptr<float>(),        \
-                           GET(dx), dres_p, g.M, g.C);                        \
-    } else {                                                                  \
-      if (need_dres)                                                          \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, true>), grid_a,     \
-                           block, 0, st, GET(x), GET(dy), GET(y),             \
-                           save_mean.data_ptr<float>(),                       \
-                           save_rstd.data_ptr<float>(), k1.data_ptr<float>(), \
-                           k2.data_ptr<float>(), k3.data_ptr<float>(),        \
-                           GET(dx), dres_p, g.M, g.C);                        \
-      else                                                                    \
-        hipLaunchKernelGGL((bn_bwd_apply_kernel<T, false, false>), grid_a,    \
-                           block, 0, st, GET(x), GET(dy), GET(y),             \
-                           save_mean.data_ptr<float>(),                       \
-                           save_rstd.data_ptr<float>(), k1.data_ptr<float>(), \
-                           k2.data_ptr<float>(), k3.data_ptr<float>(),        \
-                           GET(dx), dres_p, g.M, g.C);                        \
-    }                                                                         \
-  }
-  if (x.scalar_type() == torch::kBFloat16) {
-    BN_BWD_T(__hip_bfloat16, GET_BF16)
-  } else {
-    TORCH_CHECK(x.scalar_type() == torch::kFloat32);
-    BN_BWD_T(float, GET_F32)
-  }
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU>), grid_r, block, 0, st,
+                     bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp, sm, sr,
+                     partial_dz, partial_dzxh, g.M, g.C);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel,
+                     dim3((g.C + FIN_CH - 1) / FIN_CH),
+                     dim3(FIN_CH * FIN_LANES), 0, st, partial_dz,
+                     partial_dzxh, gm, weight.data_ptr<float>(), sr, k1, k2,
+                     k3, dweight.data_ptr<float>(), dbias.data_ptr<float>(),
+                     g.M, g.C);
+  if (need_dres)
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, RELU, true>), grid_a, block, 0,
+                       st, bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp,
+                       sm, sr, k1, k2, k3, bn_ptr<T>(dx), bn_ptr<T>(dres),
+                       g.M, g.C);
+  else
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<T, RELU, false>), grid_a, block,
+                       0, st, bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp,
+                       sm, sr, k1, k2, k3, bn_ptr<T>(dx), (T*)nullptr, g.M,
+                       g.C);
   std::vector<torch::Tensor> out = {dx, dweight, dbias};
   if (need_dres) out.push_back(dres);
   return out;
+}
+
+template <int RELU>
+std::vector<torch::Tensor> bn_bwd_dispatch(
+    const torch::Tensor& x, const torch::Tensor& dy, const torch::Tensor& yq,
+    const torch::Tensor& save_mean, const torch::Tensor& save_rstd,
+    const torch::Tensor& weight, bool need_dres,
+    const c10::optional<torch::Tensor>& ws) {
+  if (x.scalar_type() == torch::kBFloat16)
+    return bn_bwd_impl<__hip_bfloat16, RELU>(x, dy, yq, save_mean, save_rstd,
+                                             weight, need_dres, ws);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32);
+  return bn_bwd_impl<float, RELU>(x, dy, yq, save_mean, save_rstd, weight,
+                                  need_dres, ws);
+}
+
+std::vector<torch::Tensor> bn_bwd(torch::Tensor x, torch::Tensor dy,
+                                  torch::Tensor y, torch::Tensor save_mean,
+                                  torch::Tensor save_rstd,
+                                  torch::Tensor weight, bool relu,
+                                  bool need_dres,
+                                  c10::optional<torch::Tensor> ws) {
+  if (relu)
+    return bn_bwd_dispatch<BN_RELU_Y>(x, dy, y, save_mean, save_rstd, weight,
+                                      need_dres, ws);
+  return bn_bwd_dispatch<BN_RELU_NONE>(x, dy, y, save_mean, save_rstd, weight,
+                                       need_dres, ws);
+}
+
+// bn_bwd with the packed mask of bn_fwd_train_mask in place of y
+std::vector<torch::Tensor> bn_bwd_mask(torch::Tensor x, torch::Tensor dy,
+                                       torch::Tensor mask,
+                                       torch::Tensor save_mean,
+                                       torch::Tensor save_rstd,
+                                       torch::Tensor weight, bool relu,
+                                       bool need_dres,
+                                       c10::optional<torch::Tensor> ws) {
+  TORCH_CHECK(relu, "the mask is the ReLU mask: relu must be set");
+  return bn_bwd_dispatch<BN_RELU_MASK>(x, dy, mask, save_mean, save_rstd,
+                                       weight, need_dres, ws);
 }
 
 void check_f32_flat(const torch::Tensor& t, const char* name) {
@@ -955,6 +1006,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd", &bn_bwd,
         "fused NHWC batchnorm bwd (+relu-mask+dres), returns "
         "dx/dweight/dbias[/dres]");
+  m.def("bn_fwd_train_mask", &bn_fwd_train_mask,
+        "bn_fwd_train with relu that also returns the bit-packed ReLU mask "
+        "[M, C/8] uint8");
+  m.def("bn_bwd_mask", &bn_bwd_mask,
+        "bn_bwd that takes the packed mask of bn_fwd_train_mask in place of "
+        "y");
+  // rows in flight per thread in the BN reduce / finalize loops
+  m.attr("BN_RED_U") = BN_RED_U;
+  m.attr("BN_FIN_U") = BN_FIN_U;
   m.def("psgd_mq", &psgd_mq, "PowerSGD P = M @ Q (MFMA f32 16x16x4)");
   m.def("psgd_mtp", &psgd_mtp, "PowerSGD Qn = M^T @ P (MFMA f32 16x16x4)");
   m.def("psgd_decompress_ef", &psgd_decompress_ef,

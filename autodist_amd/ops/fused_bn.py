@@ -25,10 +25,17 @@ class _FusedBNFunction(torch.autograd.Function):
                 momentum, eps, relu, residual, ws=None):
         use_hip = x.is_cuda and ops_api.has_gpu_ops()
         ctx.ws_bwd = ws[1] if ws is not None else None
-        if use_hip:
+        if use_hip and relu:
+            # backward needs y only for its sign: the apply kernel packs
+            # y > 0 into one bit per element, and that mask is saved instead
+            y, save_mean, save_rstd, sign = ops_api.ext().bn_fwd_train_mask(
+                x, weight, bias, running_mean, running_var, residual,
+                eps, momentum, relu, ws[0] if ws is not None else None)
+        elif use_hip:
             y, save_mean, save_rstd = ops_api.ext().bn_fwd_train(
                 x, weight, bias, running_mean, running_var, residual,
                 eps, momentum, relu, ws[0] if ws is not None else None)
+            sign = y  # not read when relu is off
         else:
             # torch's own batch-norm kernels, so that a fused=True model is
             # the unfused model on this path down to the last bit, however
@@ -53,26 +60,29 @@ class _FusedBNFunction(torch.autograd.Function):
                 if relu:
                     y = torch.relu(y)
                 y = y.to(x.dtype)
-        ctx.save_for_backward(x, y, save_mean, save_rstd, weight)
+            sign = y
+        ctx.save_for_backward(x, sign, save_mean, save_rstd, weight)
         ctx.relu = relu
         ctx.has_res = residual is not None
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        x, y, save_mean, save_rstd, weight = ctx.saved_tensors
+        # sign: y itself, or on the HIP path with relu its packed y > 0 mask
+        x, sign, save_mean, save_rstd, weight = ctx.saved_tensors
         relu, has_res = ctx.relu, ctx.has_res
         use_hip = x.is_cuda and ops_api.has_gpu_ops()
         if use_hip:
-            out = ops_api.ext().bn_bwd(x, dy.contiguous(
-                memory_format=torch.channels_last), y, save_mean, save_rstd,
+            bwd = ops_api.ext().bn_bwd_mask if relu else ops_api.ext().bn_bwd
+            out = bwd(x, dy.contiguous(
+                memory_format=torch.channels_last), sign, save_mean, save_rstd,
                 weight, relu, has_res, ctx.ws_bwd)
             dx, dweight, dbias = out[0], out[1], out[2]
             dres = out[3] if has_res else None
         else:
             dyf = dy.float()
             if relu:
-                dyf = dyf * (y > 0).float()
+                dyf = dyf * (sign > 0).float()
             dres = dyf.to(dy.dtype) if has_res else None
             dxf, dweight, dbias = torch.ops.aten.native_batch_norm_backward(
                 dyf, x.float(), weight, None, None, save_mean, save_rstd,
