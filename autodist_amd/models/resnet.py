@@ -43,8 +43,11 @@ class Bottleneck(nn.Module):
             out = self.bn1(self.conv1(x))
             out = self.bn2(self.conv2(out))
             z = self.conv3(out)
-            identity = x if self.downsample is None else self.downsample(x)
-            return self.bn3.forward_add(z, identity)
+            if self.downsample is None:
+                return self.bn3.forward_add(z, x)
+            # downsample = (conv, ReLU-less bn): its bn joins bn3's kernel
+            return self.bn3.forward_add_bn(z, self.downsample[0](x),
+                                           self.downsample[1])
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -72,8 +75,10 @@ class BasicBlock(nn.Module):
         if self.fused:
             out = self.bn1(self.conv1(x))
             z = self.conv2(out)
-            identity = x if self.downsample is None else self.downsample(x)
-            return self.bn2.forward_add(z, identity)
+            if self.downsample is None:
+                return self.bn2.forward_add(z, x)
+            return self.bn2.forward_add_bn(z, self.downsample[0](x),
+                                           self.downsample[1])
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -121,10 +126,12 @@ class ResNet(nn.Module):
         return nn.Sequential(*layers)
 
     def forward(self, x):
-        x = self.bn1(self.conv1(x))
-        if not self.fused:
-            x = self.relu(x)
-        x = self.maxpool(x)
+        if self.fused:
+            # bn -> relu -> maxpool in the BN kernels; self.maxpool stays for
+            # the unfused path and the module structure
+            x = self.bn1.forward_pool(self.conv1(x))
+        else:
+            x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
         x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)

@@ -116,6 +116,86 @@ __device__ __forceinline__ void apply_mask8(unsigned bits, float* dv) {
   for (int k = 0; k < BN_VEC; ++k) dv[k] = (bits >> k) & 1u ? dv[k] : 0.f;
 }
 
+// v as it reads back after a store to T
+__device__ __forceinline__ float round_to(float v, const __hip_bfloat16*) {
+  return __bfloat162float(__float2bfloat16(v));
+}
+__device__ __forceinline__ float round_to(float v, const float*) { return v; }
+
+// ------------------------------------------------- 3x3 / stride 2 / pad 1 pool
+// The stem's bn -> relu -> maxpool keeps no full-resolution y. The forward
+// pool-apply kernel writes the pooled y and, per pooled pixel and 8 channels,
+// one argmax word: nibble k holds the window position kh*3+kw (0..8) of the
+// first maximum of channel c0+k (row-major window order, strict >, compared
+// after rounding to T), or BN_POOL_NONE where the pooled value is not > 0, so
+// the ReLU mask is folded in. Backward (BN_RELU_POOL) gathers dz of an input
+// pixel from the 1, 2 or 4 windows that cover it.
+#define BN_RELU_POOL 3
+#define BN_POOL_NONE 15u
+#define BN_POOL_NEVER 14u  // a code no nibble holds: a window that is not there
+struct BNPool {
+  const unsigned* amax;  // [N*Ho*Wo, C/8]
+  int H, W, Ho, Wo;
+};
+// what one input pixel needs from the pooled side: dy and the argmax word of
+// four windows in ascending (ho, wo), and the window position this pixel has
+// in each. Windows that do not exist are loaded from the first one's address
+// under a code that matches nothing, so all loads are unconditional and can
+// be issued ahead of their use.
+template <typename T>
+struct PoolTaps {
+  Raw8<T> d[4];
+  unsigned a[4];
+  unsigned codes;  // byte j: the position of the pixel in window j
+};
+template <typename T>
+__device__ __forceinline__ void pool_issue(const T* __restrict__ dy,
+                                           const BNPool& p, long m, int C,
+                                           int c0, PoolTaps<T>& t) {
+  // N*H*W and the pooled tensor's element count are below 2^31 (checked by
+  // the host): 32-bit divisions, and one 32-bit offset per window, which
+  // addresses dy and, divided by 8, the argmax word
+  const unsigned mm = (unsigned)m;
+  const unsigned q = mm / (unsigned)p.W;
+  const int w = (int)(mm - q * (unsigned)p.W);
+  const unsigned n = q / (unsigned)p.H;
+  const int h = (int)(q - n * (unsigned)p.H);
+  // window ho covers rows 2ho-1..2ho+1: an even h lies in window h/2 alone
+  // (kh = 1), an odd h in (h-1)/2 (kh = 2) and, if it exists, (h+1)/2 (kh = 0)
+  const int ho = h >> 1, wo = w >> 1;
+  const bool hb = (h & 1) && ho + 1 < p.Ho;
+  const bool wb = (w & 1) && wo + 1 < p.Wo;
+  const unsigned kh = 1 + (h & 1), kw = 1 + (w & 1);
+  const unsigned o0 = ((n * p.Ho + ho) * p.Wo + wo) * C + c0;
+  const unsigned dh = hb ? p.Wo * C : 0, dw = wb ? C : 0;
+  const unsigned o[4] = {o0, o0 + dw, o0 + dh, o0 + dh + dw};
+  t.codes = (kh * 3 + kw) | (wb ? kh * 3 : BN_POOL_NEVER) << 8 |
+            (hb ? kw : BN_POOL_NEVER) << 16 |
+            (hb && wb ? 0u : BN_POOL_NEVER) << 24;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    t.d[j] = load8raw(dy + o[j]);
+    t.a[j] = p.amax[o[j] / BN_VEC];
+  }
+}
+// dz = the pooled dy of the windows whose nibble names this pixel, added in
+// fp32 in ascending (ho, wo) and rounded once to T
+template <typename T>
+__device__ __forceinline__ void pool_dz(const PoolTaps<T>& t, float* dv) {
+  float acc[BN_VEC] = {0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float d[BN_VEC];
+    unpack8(t.d[j], d);
+    const unsigned e = t.a[j] ^ (((t.codes >> (8 * j)) & 15u) * 0x11111111u);
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k)
+      acc[k] += ((e >> (4 * k)) & 15u) == 0u ? d[k] : 0.f;
+  }
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) dv[k] = round_to(acc[k], (const T*)nullptr);
+}
+
 // ---------------------------------------------------------------- fwd reduce
 // Two-stage, atomic-free (deterministic): each block writes one partial row
 // partial[blockIdx.x][c]; the finalize kernel sums the gridM rows. (A global
@@ -298,15 +378,136 @@ __global__ void bn_fwd_apply_kernel(const T* __restrict__ x,
   }
 }
 
+// ---------------------------------------------------- fwd apply + max-pool
+// A thread owns 8 channels of one pooled pixel (mo = (n*Ho + ho)*Wo + wo). It
+// forms relu(x*scale+shift) rounded to T, the values bn_fwd_apply_kernel
+// stores, at the window's nine positions and keeps the first maximum.
+// Positions outside the image are loaded from the nearest pixel inside (the
+// centre always is) and skipped, so the nine loads are unconditional.
+// x*scale+shift is spelled fmaf here and in bn_fwd_apply_add_bn_kernel:
+// bn_fwd_apply_kernel writes v*sc+sh and the compiler contracts it to one
+// fused multiply-add (v_pk_fma_f32). The pooled y and the joint tail are
+// bit-equal to the split path only while that kernel stays contracted;
+// tests/test_bn_pool_gpu.py and tests/test_bn_add_bn_gpu.py fail otherwise.
+template <typename T>
+__global__ void bn_fwd_pool_apply_kernel(const T* __restrict__ x,
+                                         T* __restrict__ y,
+                                         unsigned* __restrict__ amax,
+                                         const float* __restrict__ scale,
+                                         const float* __restrict__ shift,
+                                         BNPool p, long Mo, int C) {
+  int tx_count = min(C / BN_VEC, (int)blockDim.x);
+  int tx = threadIdx.x % tx_count;
+  int ty = threadIdx.x / tx_count;
+  int rows_per_blk = blockDim.x / tx_count;
+  int c0 = (blockIdx.y * tx_count + tx) * BN_VEC;
+  if (c0 >= C) return;
+  float sc[BN_VEC], sh[BN_VEC];
+  load8(scale + c0, sc);
+  load8(shift + c0, sh);
+  for (long mo = (long)blockIdx.x * rows_per_blk + ty; mo < Mo;
+       mo += (long)gridDim.x * rows_per_blk) {
+    const unsigned mm = (unsigned)mo;  // < 2^31, checked by the host
+    const unsigned q = mm / (unsigned)p.Wo;
+    const int wo = (int)(mm - q * (unsigned)p.Wo);
+    const unsigned n = q / (unsigned)p.Ho;
+    const int ho = (int)(q - n * (unsigned)p.Ho);
+    Raw8<T> rx[9];
+    bool ok[9];
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh) {
+      const int h = 2 * ho - 1 + kh;
+      const int hc = min(max(h, 0), p.H - 1);
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const int w = 2 * wo - 1 + kw;
+        const int wc = min(max(w, 0), p.W - 1);
+        ok[kh * 3 + kw] = h == hc && w == wc;
+        rx[kh * 3 + kw] =
+            load8raw(x + (((long)n * p.H + hc) * p.W + wc) * C + c0);
+      }
+    }
+    float best[BN_VEC];
+    unsigned idx[BN_VEC];
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) { best[k] = -1.f; idx[k] = 0; }
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      float v[BN_VEC];
+      unpack8(rx[j], v);
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) {
+        float r = round_to(fmaxf(fmaf(v[k], sc[k], sh[k]), 0.f),
+                           (const T*)nullptr);
+        const bool take = ok[j] && r > best[k];
+        best[k] = take ? r : best[k];
+        idx[k] = take ? (unsigned)j : idx[k];
+      }
+    }
+    unsigned word = 0;
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k)
+      word |= (best[k] > 0.f ? idx[k] : BN_POOL_NONE) << (4 * k);
+    store8(y + mo * C + c0, best);
+    amax[mo * (C / BN_VEC) + c0 / BN_VEC] = word;
+  }
+}
+
+// ------------------------------------- fwd apply, block tail with two BNs
+// y = relu(bn3(z) + bn_ds(zd)) and its packed mask. The inner value is
+// rounded to T first: it is the identity tensor that the plain apply kernel
+// would have stored and the ADD variant read back.
+template <typename T>
+__global__ void bn_fwd_apply_add_bn_kernel(
+    const T* __restrict__ z, const T* __restrict__ zd, T* __restrict__ y,
+    unsigned char* __restrict__ mask, const float* __restrict__ scale,
+    const float* __restrict__ shift, const float* __restrict__ scale_d,
+    const float* __restrict__ shift_d, long M, int C) {
+  int tx_count = min(C / BN_VEC, (int)blockDim.x);
+  int tx = threadIdx.x % tx_count;
+  int ty = threadIdx.x / tx_count;
+  int rows_per_blk = blockDim.x / tx_count;
+  int c0 = (blockIdx.y * tx_count + tx) * BN_VEC;
+  if (c0 >= C) return;
+  float sc[BN_VEC], sh[BN_VEC], scd[BN_VEC], shd[BN_VEC];
+  load8(scale + c0, sc);
+  load8(shift + c0, sh);
+  load8(scale_d + c0, scd);
+  load8(shift_d + c0, shd);
+  for (long m = (long)blockIdx.x * rows_per_blk + ty; m < M;
+       m += (long)gridDim.x * rows_per_blk) {
+    float v[BN_VEC], r[BN_VEC];
+    load8(z + m * C + c0, v);
+    load8(zd + m * C + c0, r);
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) {
+      v[k] = fmaf(v[k], sc[k], sh[k]);
+      v[k] += round_to(fmaf(r[k], scd[k], shd[k]), (const T*)nullptr);
+      v[k] = fmaxf(v[k], 0.f);
+    }
+    mask[m * (C / BN_VEC) + c0 / BN_VEC] =
+        (unsigned char)store8_mask(y + m * C + c0, v);
+  }
+}
+
 // ------------------------------------------------------------- bwd reduce
 // dz = RELU ? (y>0 ? dy : 0) : dy ; accumulate sum_dz, sum_dz*xhat.
 // RELU is BN_RELU_NONE, BN_RELU_Y (y > 0 from the stored y) or BN_RELU_MASK
-// (the same bit, read from the forward's packed mask: 1 byte, not 8 values).
+// (the same bit, read from the forward's packed mask: 1 byte, not 8 values)
+// or BN_RELU_POOL (dy is the pooled dy: dz is gathered through the argmax
+// words of pool, see pool_issue / pool_dz).
 template <typename T, int RELU>
 __device__ __forceinline__ void bn_load_dz(const T* __restrict__ dy,
                                            const T* __restrict__ y,
                                            const unsigned char* __restrict__ mask,
-                                           long m, int C, int c0, float* dv) {
+                                           const BNPool& pool, long m, int C,
+                                           int c0, float* dv) {
+  if (RELU == BN_RELU_POOL) {
+    PoolTaps<T> t;
+    pool_issue(dy, pool, m, C, c0, t);
+    pool_dz(t, dv);
+    return;
+  }
   load8(dy + m * C + c0, dv);
   if (RELU == BN_RELU_Y) {
     float yv[BN_VEC];
@@ -320,13 +521,15 @@ __device__ __forceinline__ void bn_load_dz(const T* __restrict__ dy,
 
 template <typename T, int RELU>
 __global__ void __launch_bounds__(BLOCK_THREADS)
+__attribute__((amdgpu_waves_per_eu(RELU == BN_RELU_POOL ? 2 : 1)))
 bn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                      const T* __restrict__ y,
                      const unsigned char* __restrict__ mask,
                      const float* __restrict__ save_mean,
                      const float* __restrict__ save_rstd,
                      float* __restrict__ partial_dz,
-                     float* __restrict__ partial_dzxh, long M, int C) {
+                     float* __restrict__ partial_dzxh, long M, int C,
+                     BNPool pool) {
 #pragma clang fp contract(off)  // see bn_fwd_reduce_kernel
   int tx_count = min(C / BN_VEC, (int)blockDim.x);
   int tx = threadIdx.x % tx_count;
@@ -343,11 +546,19 @@ bn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
   for (; m + (BN_RED_U - 1) * stride < M; m += BN_RED_U * stride) {
     Raw8<T> rx[BN_RED_U], rd[BN_RED_U], ry[BN_RED_U];
     unsigned rm[BN_RED_U];
+    PoolTaps<T> rp[BN_RED_U];
 #pragma unroll
     for (int u = 0; u < BN_RED_U; ++u) {
       const long mu = m + u * stride;
       rx[u] = load8raw(x + mu * C + c0);
-      rd[u] = load8raw(dy + mu * C + c0);
+      if (RELU == BN_RELU_POOL) {
+        pool_issue(dy, pool, mu, C, c0, rp[u]);
+        // issue this row's nine loads before the next row's addresses are
+        // formed: 36 addresses held at once cost more registers than the data
+        __builtin_amdgcn_sched_barrier(0);
+      } else {
+        rd[u] = load8raw(dy + mu * C + c0);
+      }
       if (RELU == BN_RELU_Y) ry[u] = load8raw(y + mu * C + c0);
       if (RELU == BN_RELU_MASK) rm[u] = mask[mu * (C / BN_VEC) + c0 / BN_VEC];
     }
@@ -357,7 +568,8 @@ bn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
     for (int u = 0; u < BN_RED_U; ++u) {
       float xv[BN_VEC], dv[BN_VEC];
       unpack8(rx[u], xv);
-      unpack8(rd[u], dv);
+      if (RELU == BN_RELU_POOL) pool_dz(rp[u], dv);
+      else unpack8(rd[u], dv);
       if (RELU == BN_RELU_Y) {
         float yv[BN_VEC];
         unpack8(ry[u], yv);
@@ -370,12 +582,15 @@ bn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
         s[k] += dv[k];
         t[k] = fmaf(dv[k] * (xv[k] - mean[k]), rstd[k], t[k]);
       }
+      // one row's taps unpacked at a time: interleaved, the four rows' 128
+      // unpacked values do not fit beside the loads still in flight
+      if (RELU == BN_RELU_POOL) __builtin_amdgcn_sched_barrier(0);
     }
   }
   for (; m < M; m += stride) {
     float xv[BN_VEC], dv[BN_VEC];
     load8(x + m * C + c0, xv);
-    bn_load_dz<T, RELU>(dy, y, mask, m, C, c0, dv);
+    bn_load_dz<T, RELU>(dy, y, mask, pool, m, C, c0, dv);
 #pragma unroll
     for (int k = 0; k < BN_VEC; ++k) {
       s[k] += dv[k];
@@ -451,7 +666,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x,
                                     const float* __restrict__ k2,
                                     const float* __restrict__ k3,
                                     T* __restrict__ dx, T* __restrict__ dres,
-                                    long M, int C) {
+                                    long M, int C, BNPool pool) {
   int tx_count = min(C / BN_VEC, (int)blockDim.x);
   int tx = threadIdx.x % tx_count;
   int ty = threadIdx.x / tx_count;
@@ -468,7 +683,7 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x,
        m += (long)gridDim.x * rows_per_blk) {
     float xv[BN_VEC], dv[BN_VEC];
     load8(x + m * C + c0, xv);
-    bn_load_dz<T, RELU>(dy, y, mask, m, C, c0, dv);
+    bn_load_dz<T, RELU>(dy, y, mask, pool, m, C, c0, dv);
     if (ADD) store8(dres + m * C + c0, dv);
     float o[BN_VEC];
 #pragma unroll

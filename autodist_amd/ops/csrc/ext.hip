@@ -78,15 +78,25 @@ void bn_launch_fwd_apply(dim3 grid, hipStream_t st, const torch::Tensor& x,
                      bn_ptr<T>(y), mask, scale, shift, g.M, g.C);
 }
 
-// with_mask: also return the bit-packed ReLU mask of y ([M, C/8] uint8, see
-// bn_fwd_apply_kernel), which bn_bwd_mask takes in place of y.
+// The statistics stage of every forward entry point: reduce and finalize on
+// x. scale / shift point into the workspace and feed the apply kernel that
+// the caller launches next on the same stream.
+struct BNStats {
+  torch::Tensor save_mean, save_rstd;
+  const float* scale;
+  const float* shift;
+  // the workspace, held until the caller has allocated its outputs and
+  // launched the apply kernel: when it is a temporary of this call, an
+  // output allocated after its release could be given its memory
+  torch::Tensor ws;
+};
+
 template <typename T>
-std::vector<torch::Tensor> bn_fwd_impl(
-    const torch::Tensor& x, const torch::Tensor& weight,
-    const torch::Tensor& bias, torch::Tensor& running_mean,
-    torch::Tensor& running_var, const c10::optional<torch::Tensor>& res,
-    double eps, double momentum, bool relu,
-    const c10::optional<torch::Tensor>& ws, bool with_mask) {
+BNStats bn_fwd_stats(const torch::Tensor& x, const BNGeom& g,
+                     const torch::Tensor& weight, const torch::Tensor& bias,
+                     torch::Tensor& running_mean, torch::Tensor& running_var,
+                     double eps, double momentum,
+                     const c10::optional<torch::Tensor>& ws) {
   // ws: persistent per-module workspace [2*BN_GM_MAX + 4, C] fp32:
   //   rows [0, GM)               partial sums (per reduce block)
   //   rows [BN_GM_MAX, BN_GM_MAX+GM) partial sumsq
@@ -98,8 +108,6 @@ std::vector<torch::Tensor> bn_fwd_impl(
   // module called twice before backward (shared tower, micro-batches summed
   // into one loss) would otherwise hand the first backward the second
   // call's stats.
-  TORCH_CHECK(!with_mask || relu, "the mask is the ReLU mask: relu must be set");
-  auto g = bn_geom(x);
   auto fopt = weight.options().dtype(torch::kFloat32);
   torch::Tensor w6 = ws.has_value() ? *ws
       : torch::empty({2 * BN_GM_MAX + 4, (long)g.C}, fopt);
@@ -113,17 +121,10 @@ std::vector<torch::Tensor> bn_fwd_impl(
   auto stats = torch::empty({2, (long)g.C}, fopt);
   auto save_mean = stats[0];
   auto save_rstd = stats[1];
-  torch::Tensor mask;
-  if (with_mask)
-    mask = torch::empty({g.M, (long)(g.C / BN_VEC)},
-                        x.options().dtype(torch::kUInt8));
-  unsigned char* mp = with_mask ? mask.data_ptr<unsigned char>() : nullptr;
   const float* scale = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
   const float* shift = wp + (long)(2 * BN_GM_MAX + 3) * g.C;
-  auto y = torch::empty_like(x);
   int gm = bn_reduce_gm(g);
   dim3 grid_r(gm, g.grid_c);
-  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
   auto st = cur_stream();
 
   hipLaunchKernelGGL((bn_fwd_reduce_kernel<T>), grid_r, dim3(BLOCK_THREADS),
@@ -138,6 +139,33 @@ std::vector<torch::Tensor> bn_fwd_impl(
                      save_mean.data_ptr<float>(), save_rstd.data_ptr<float>(),
                      const_cast<float*>(scale), const_cast<float*>(shift),
                      g.M, g.C, (float)eps, (float)momentum);
+  return {save_mean, save_rstd, scale, shift, w6};
+}
+
+// with_mask: also return the bit-packed ReLU mask of y ([M, C/8] uint8, see
+// bn_fwd_apply_kernel), which bn_bwd_mask takes in place of y.
+template <typename T>
+std::vector<torch::Tensor> bn_fwd_impl(
+    const torch::Tensor& x, const torch::Tensor& weight,
+    const torch::Tensor& bias, torch::Tensor& running_mean,
+    torch::Tensor& running_var, const c10::optional<torch::Tensor>& res,
+    double eps, double momentum, bool relu,
+    const c10::optional<torch::Tensor>& ws, bool with_mask) {
+  TORCH_CHECK(!with_mask || relu, "the mask is the ReLU mask: relu must be set");
+  auto g = bn_geom(x);
+  BNStats s = bn_fwd_stats<T>(x, g, weight, bias, running_mean, running_var,
+                              eps, momentum, ws);
+  auto save_mean = s.save_mean, save_rstd = s.save_rstd;
+  const float* scale = s.scale;
+  const float* shift = s.shift;
+  torch::Tensor mask;
+  if (with_mask)
+    mask = torch::empty({g.M, (long)(g.C / BN_VEC)},
+                        x.options().dtype(torch::kUInt8));
+  unsigned char* mp = with_mask ? mask.data_ptr<unsigned char>() : nullptr;
+  auto y = torch::empty_like(x);
+  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  auto st = cur_stream();
   const torch::Tensor* rp = res.has_value() ? &*res : nullptr;
 #define BN_FWD_APPLY(RELU, ADD, MASK)                                        \
   bn_launch_fwd_apply<T, RELU, ADD, MASK>(grid_a, st, x, rp, y, mp, scale,  \
@@ -193,6 +221,115 @@ std::vector<torch::Tensor> bn_fwd_train_mask(
                          momentum, relu, ws, true);
 }
 
+// ------------------------------------------- bn + relu + 3x3/s2/p1 max-pool
+inline BNPool bn_pool_geom(const torch::Tensor& x, const BNGeom& g) {
+  BNPool p;
+  p.amax = nullptr;
+  p.H = (int)x.size(2);
+  p.W = (int)x.size(3);
+  p.Ho = (p.H - 1) / 2 + 1;
+  p.Wo = (p.W - 1) / 2 + 1;
+  // the kernels index pixels, and the pooled tensor's elements, in 32 bits
+  TORCH_CHECK(g.M < (1L << 31), "bn pool: N*H*W must be below 2^31");
+  TORCH_CHECK(x.size(0) * (long)p.Ho * p.Wo * g.C < (1L << 31),
+              "bn pool: the pooled tensor must hold fewer than 2^31 elements");
+  return p;
+}
+
+// -> (pooled y, save_mean, save_rstd, argmax [N*Ho*Wo, C/8] int32)
+template <typename T>
+std::vector<torch::Tensor> bn_fwd_pool_impl(
+    const torch::Tensor& x, const torch::Tensor& weight,
+    const torch::Tensor& bias, torch::Tensor& running_mean,
+    torch::Tensor& running_var, double eps, double momentum,
+    const c10::optional<torch::Tensor>& ws) {
+  auto g = bn_geom(x);
+  BNPool p = bn_pool_geom(x, g);
+  BNStats s = bn_fwd_stats<T>(x, g, weight, bias, running_mean, running_var,
+                              eps, momentum, ws);
+  BNGeom go = g;
+  go.M = x.size(0) * (long)p.Ho * p.Wo;
+  auto y = torch::empty({x.size(0), x.size(1), (long)p.Ho, (long)p.Wo},
+                        x.options().memory_format(at::MemoryFormat::ChannelsLast));
+  auto amax = torch::empty({go.M, (long)(g.C / BN_VEC)},
+                           x.options().dtype(torch::kInt32));
+  dim3 grid_a(bn_grid_m(go, 4096), g.grid_c);
+  hipLaunchKernelGGL((bn_fwd_pool_apply_kernel<T>), grid_a,
+                     dim3(BLOCK_THREADS), 0, cur_stream(), bn_ptr<const T>(x),
+                     bn_ptr<T>(y), bn_ptr<unsigned>(amax), s.scale, s.shift,
+                     p, go.M, g.C);
+  return {y, s.save_mean, s.save_rstd, amax};
+}
+
+std::vector<torch::Tensor> bn_fwd_train_pool(
+    torch::Tensor x, torch::Tensor weight, torch::Tensor bias,
+    torch::Tensor running_mean, torch::Tensor running_var, double eps,
+    double momentum, c10::optional<torch::Tensor> ws) {
+  if (x.scalar_type() == torch::kBFloat16)
+    return bn_fwd_pool_impl<__hip_bfloat16>(x, weight, bias, running_mean,
+                                            running_var, eps, momentum, ws);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32);
+  return bn_fwd_pool_impl<float>(x, weight, bias, running_mean, running_var,
+                                 eps, momentum, ws);
+}
+
+// ------------------------------------ block tail: relu(bn3(z) + bn_ds(zd))
+// -> (y, mask, save_mean, save_rstd, save_mean_d, save_rstd_d). Each BN runs
+// its statistics in its own workspace; one apply kernel joins them. Backward
+// is bn_bwd_mask on (z, bn3 stats) and on (zd, downsample stats), both with
+// the dy and the mask of y.
+template <typename T>
+std::vector<torch::Tensor> bn_fwd_add_bn_impl(
+    const torch::Tensor& z, const torch::Tensor& zd,
+    const torch::Tensor& weight, const torch::Tensor& bias,
+    torch::Tensor& running_mean, torch::Tensor& running_var, double eps,
+    double momentum, const c10::optional<torch::Tensor>& ws,
+    const torch::Tensor& weight_d, const torch::Tensor& bias_d,
+    torch::Tensor& running_mean_d, torch::Tensor& running_var_d, double eps_d,
+    double momentum_d, const c10::optional<torch::Tensor>& ws_d) {
+  auto g = bn_geom(z);
+  auto gd = bn_geom(zd);
+  TORCH_CHECK(zd.sizes() == z.sizes() && zd.scalar_type() == z.scalar_type() &&
+                  zd.device() == z.device() && gd.M == g.M,
+              "bn_fwd_train_add_bn: z and zd must agree in shape and dtype");
+  TORCH_CHECK(!ws.has_value() || !ws_d.has_value() ||
+                  ws->data_ptr() != ws_d->data_ptr(),
+              "bn_fwd_train_add_bn: the two BNs need workspaces of their own");
+  BNStats s = bn_fwd_stats<T>(z, g, weight, bias, running_mean, running_var,
+                              eps, momentum, ws);
+  BNStats sd = bn_fwd_stats<T>(zd, gd, weight_d, bias_d, running_mean_d,
+                               running_var_d, eps_d, momentum_d, ws_d);
+  auto y = torch::empty_like(z);
+  auto mask = torch::empty({g.M, (long)(g.C / BN_VEC)},
+                           z.options().dtype(torch::kUInt8));
+  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  hipLaunchKernelGGL((bn_fwd_apply_add_bn_kernel<T>), grid_a,
+                     dim3(BLOCK_THREADS), 0, cur_stream(), bn_ptr<const T>(z),
+                     bn_ptr<const T>(zd), bn_ptr<T>(y),
+                     mask.data_ptr<unsigned char>(), s.scale, s.shift,
+                     sd.scale, sd.shift, g.M, g.C);
+  return {y, mask, s.save_mean, s.save_rstd, sd.save_mean, sd.save_rstd};
+}
+
+std::vector<torch::Tensor> bn_fwd_train_add_bn(
+    torch::Tensor z, torch::Tensor zd, torch::Tensor weight,
+    torch::Tensor bias, torch::Tensor running_mean, torch::Tensor running_var,
+    double eps, double momentum, c10::optional<torch::Tensor> ws,
+    torch::Tensor weight_d, torch::Tensor bias_d, torch::Tensor running_mean_d,
+    torch::Tensor running_var_d, double eps_d, double momentum_d,
+    c10::optional<torch::Tensor> ws_d) {
+  if (z.scalar_type() == torch::kBFloat16)
+    return bn_fwd_add_bn_impl<__hip_bfloat16>(
+        z, zd, weight, bias, running_mean, running_var, eps, momentum, ws,
+        weight_d, bias_d, running_mean_d, running_var_d, eps_d, momentum_d,
+        ws_d);
+  TORCH_CHECK(z.scalar_type() == torch::kFloat32);
+  return bn_fwd_add_bn_impl<float>(
+      z, zd, weight, bias, running_mean, running_var, eps, momentum, ws,
+      weight_d, bias_d, running_mean_d, running_var_d, eps_d, momentum_d,
+      ws_d);
+}
+
 // RELU: BN_RELU_NONE / BN_RELU_Y (yq is y, same dtype and layout as x) /
 // BN_RELU_MASK (yq is the forward's packed mask).
 template <typename T, int RELU>
@@ -242,7 +379,7 @@ std::vector<torch::Tensor> bn_bwd_impl(
 
   hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, RELU>), grid_r, block, 0, st,
                      bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp, sm, sr,
-                     partial_dz, partial_dzxh, g.M, g.C);
+                     partial_dz, partial_dzxh, g.M, g.C, BNPool{});
   hipLaunchKernelGGL(bn_bwd_finalize_kernel,
                      dim3((g.C + FIN_CH - 1) / FIN_CH),
                      dim3(FIN_CH * FIN_LANES), 0, st, partial_dz,
@@ -253,12 +390,12 @@ std::vector<torch::Tensor> bn_bwd_impl(
     hipLaunchKernelGGL((bn_bwd_apply_kernel<T, RELU, true>), grid_a, block, 0,
                        st, bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp,
                        sm, sr, k1, k2, k3, bn_ptr<T>(dx), bn_ptr<T>(dres),
-                       g.M, g.C);
+                       g.M, g.C, BNPool{});
   else
     hipLaunchKernelGGL((bn_bwd_apply_kernel<T, RELU, false>), grid_a, block,
                        0, st, bn_ptr<const T>(x), bn_ptr<const T>(dy), yp, mp,
                        sm, sr, k1, k2, k3, bn_ptr<T>(dx), (T*)nullptr, g.M,
-                       g.C);
+                       g.C, BNPool{});
   std::vector<torch::Tensor> out = {dx, dweight, dbias};
   if (need_dres) out.push_back(dres);
   return out;
@@ -302,6 +439,84 @@ std::vector<torch::Tensor> bn_bwd_mask(torch::Tensor x, torch::Tensor dy,
   TORCH_CHECK(relu, "the mask is the ReLU mask: relu must be set");
   return bn_bwd_dispatch<BN_RELU_MASK>(x, dy, mask, save_mean, save_rstd,
                                        weight, need_dres, ws);
+}
+
+// bn_bwd for bn_fwd_train_pool: dy is the pooled dy, argmax the forward's
+// argmax words; the kernels gather dz through them (BN_RELU_POOL).
+// -> (dx, dweight, dbias)
+template <typename T>
+std::vector<torch::Tensor> bn_bwd_pool_impl(
+    const torch::Tensor& x, const torch::Tensor& dy,
+    const torch::Tensor& argmax, const torch::Tensor& save_mean,
+    const torch::Tensor& save_rstd, const torch::Tensor& weight,
+    const c10::optional<torch::Tensor>& ws) {
+  auto g = bn_geom(x);
+  BNPool p = bn_pool_geom(x, g);
+  const long Mo = x.size(0) * (long)p.Ho * p.Wo;
+  TORCH_CHECK(dy.dim() == 4 && dy.size(0) == x.size(0) && dy.size(1) == g.C &&
+                  dy.size(2) == p.Ho && dy.size(3) == p.Wo &&
+                  dy.scalar_type() == x.scalar_type() &&
+                  dy.device() == x.device() &&
+                  dy.is_contiguous(at::MemoryFormat::ChannelsLast),
+              "dy must be the channels_last [N, C, Ho, Wo] gradient of the "
+              "pooled y");
+  TORCH_CHECK(argmax.scalar_type() == torch::kInt32 && argmax.is_contiguous() &&
+                  argmax.dim() == 2 && argmax.size(0) == Mo &&
+                  argmax.size(1) == g.C / BN_VEC &&
+                  argmax.device() == x.device(),
+              "argmax must be the [N*Ho*Wo, C/8] int32 tensor of "
+              "bn_fwd_train_pool");
+  p.amax = bn_ptr<const unsigned>(argmax);
+  auto fopt = weight.options().dtype(torch::kFloat32);
+  torch::Tensor w5 = ws.has_value() ? *ws
+      : torch::empty({2 * BN_GM_MAX + 3, (long)g.C}, fopt);
+  TORCH_CHECK(w5.size(0) >= 2 * BN_GM_MAX + 3 && w5.size(1) == g.C &&
+              w5.is_contiguous());
+  float* wp = w5.data_ptr<float>();
+  float* partial_dz = wp;
+  float* partial_dzxh = wp + (long)BN_GM_MAX * g.C;
+  float* k1 = wp + (long)(2 * BN_GM_MAX + 0) * g.C;
+  float* k2 = wp + (long)(2 * BN_GM_MAX + 1) * g.C;
+  float* k3 = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
+  auto dweight = torch::empty({g.C}, fopt);
+  auto dbias = torch::empty({g.C}, fopt);
+  auto dx = torch::empty_like(x);
+  dim3 block(BLOCK_THREADS);
+  int gm = bn_reduce_gm(g);
+  dim3 grid_r(gm, g.grid_c);
+  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  auto st = cur_stream();
+  const float* sm = save_mean.data_ptr<float>();
+  const float* sr = save_rstd.data_ptr<float>();
+  hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, BN_RELU_POOL>), grid_r, block, 0,
+                     st, bn_ptr<const T>(x), bn_ptr<const T>(dy),
+                     (const T*)nullptr, (const unsigned char*)nullptr, sm, sr,
+                     partial_dz, partial_dzxh, g.M, g.C, p);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel,
+                     dim3((g.C + FIN_CH - 1) / FIN_CH),
+                     dim3(FIN_CH * FIN_LANES), 0, st, partial_dz,
+                     partial_dzxh, gm, weight.data_ptr<float>(), sr, k1, k2,
+                     k3, dweight.data_ptr<float>(), dbias.data_ptr<float>(),
+                     g.M, g.C);
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, BN_RELU_POOL, false>), grid_a,
+                     block, 0, st, bn_ptr<const T>(x), bn_ptr<const T>(dy),
+                     (const T*)nullptr, (const unsigned char*)nullptr, sm, sr,
+                     k1, k2, k3, bn_ptr<T>(dx), (T*)nullptr, g.M, g.C, p);
+  return {dx, dweight, dbias};
+}
+
+std::vector<torch::Tensor> bn_bwd_pool(torch::Tensor x, torch::Tensor dy,
+                                       torch::Tensor argmax,
+                                       torch::Tensor save_mean,
+                                       torch::Tensor save_rstd,
+                                       torch::Tensor weight,
+                                       c10::optional<torch::Tensor> ws) {
+  if (x.scalar_type() == torch::kBFloat16)
+    return bn_bwd_pool_impl<__hip_bfloat16>(x, dy, argmax, save_mean,
+                                            save_rstd, weight, ws);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32);
+  return bn_bwd_pool_impl<float>(x, dy, argmax, save_mean, save_rstd, weight,
+                                 ws);
 }
 
 void check_f32_flat(const torch::Tensor& t, const char* name) {
@@ -1012,6 +1227,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_mask", &bn_bwd_mask,
         "bn_bwd that takes the packed mask of bn_fwd_train_mask in place of "
         "y");
+  m.def("bn_fwd_train_pool", &bn_fwd_train_pool,
+        "bn + relu + 3x3/stride 2/pad 1 max-pool: (x, weight, bias, "
+        "running_mean, running_var, eps, momentum, ws) -> (pooled y, "
+        "save_mean, save_rstd, argmax words)");
+  m.def("bn_bwd_pool", &bn_bwd_pool,
+        "backward of bn_fwd_train_pool: (x, dy_pooled, argmax, save_mean, "
+        "save_rstd, weight, ws) -> (dx, dweight, dbias)");
+  m.def("bn_fwd_train_add_bn", &bn_fwd_train_add_bn,
+        "relu(bn(z) + bn_d(zd)): (z, zd, then weight, bias, running_mean, "
+        "running_var, eps, momentum, ws of each BN) -> (y, mask, save_mean, "
+        "save_rstd, save_mean_d, save_rstd_d)");
   // rows in flight per thread in the BN reduce / finalize loops
   m.attr("BN_RED_U") = BN_RED_U;
   m.attr("BN_FIN_U") = BN_FIN_U;

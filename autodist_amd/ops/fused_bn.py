@@ -19,6 +19,12 @@ import torch
 from autodist_amd.ops import api as ops_api
 
 
+# True routes forward_pool / forward_add_bn through the separate kernels they
+# replace (bn -> F.max_pool2d, bn_ds -> bn.forward_add): the A/B switch of
+# tools/bn_microbench.py and the reference of the GPU tests.
+SPLIT_PATH = False
+
+
 class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
@@ -91,6 +97,60 @@ class _FusedBNFunction(torch.autograd.Function):
         return (dx, dweight, dbias, None, None, None, None, None, dres, None)
 
 
+class _FusedBNPoolFunction(torch.autograd.Function):
+    """bn -> relu -> 3x3/stride 2/pad 1 max-pool on the HIP kernels. Saves x,
+    the argmax words, the statistics and the weight: no full-resolution y."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, momentum,
+                eps, ws):
+        y, save_mean, save_rstd, argmax = ops_api.ext().bn_fwd_train_pool(
+            x, weight, bias, running_mean, running_var, eps, momentum,
+            ws[0] if ws is not None else None)
+        ctx.ws_bwd = ws[1] if ws is not None else None
+        ctx.save_for_backward(x, argmax, save_mean, save_rstd, weight)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, argmax, save_mean, save_rstd, weight = ctx.saved_tensors
+        dx, dweight, dbias = ops_api.ext().bn_bwd_pool(
+            x, dy.contiguous(memory_format=torch.channels_last), argmax,
+            save_mean, save_rstd, weight, ctx.ws_bwd)
+        return dx, dweight, dbias, None, None, None, None, None
+
+
+class _FusedBNAddBNFunction(torch.autograd.Function):
+    """relu(bn(z) + bn_d(zd)) with one apply kernel; backward is bn_bwd_mask
+    on each branch, both with the dy and the packed mask of y."""
+
+    @staticmethod
+    def forward(ctx, z, zd, weight, bias, running_mean, running_var, momentum,
+                eps, ws, weight_d, bias_d, running_mean_d, running_var_d,
+                momentum_d, eps_d, ws_d):
+        y, mask, sm, sr, sm_d, sr_d = ops_api.ext().bn_fwd_train_add_bn(
+            z, zd, weight, bias, running_mean, running_var, eps, momentum,
+            ws[0] if ws is not None else None,
+            weight_d, bias_d, running_mean_d, running_var_d, eps_d,
+            momentum_d, ws_d[0] if ws_d is not None else None)
+        ctx.ws_bwd = ws[1] if ws is not None else None
+        ctx.ws_bwd_d = ws_d[1] if ws_d is not None else None
+        ctx.save_for_backward(z, zd, mask, sm, sr, sm_d, sr_d, weight,
+                              weight_d)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        z, zd, mask, sm, sr, sm_d, sr_d, weight, weight_d = ctx.saved_tensors
+        dy = dy.contiguous(memory_format=torch.channels_last)
+        bwd = ops_api.ext().bn_bwd_mask
+        dz, dw, db = bwd(z, dy, mask, sm, sr, weight, True, False, ctx.ws_bwd)
+        dzd, dw_d, db_d = bwd(zd, dy, mask, sm_d, sr_d, weight_d, True, False,
+                              ctx.ws_bwd_d)
+        return (dz, dzd, dw, db, None, None, None, None, None,
+                dw_d, db_d, None, None, None, None, None)
+
+
 def fused_bn_train(x, weight, bias, running_mean, running_var,
                    momentum=0.1, eps=1e-5, relu=False,
                    residual: Optional[torch.Tensor] = None, ws=None):
@@ -102,7 +162,9 @@ class FusedBatchNorm2d(torch.nn.Module):
     """Drop-in BatchNorm2d with optional fused ReLU and residual add.
 
     forward(x) applies bn [+relu]; forward_add(x, residual) applies
-    bn(x) + residual -> relu (the Bottleneck tail).
+    bn(x) + residual -> relu (the Bottleneck tail); forward_pool(x) applies
+    bn -> relu -> 3x3/2 max-pool (the ResNet stem); forward_add_bn(z, zd, bn_d)
+    applies relu(bn(z) + bn_d(zd)) (the tail of a block with a downsample).
     """
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, relu=False):
@@ -124,28 +186,30 @@ class FusedBatchNorm2d(torch.nn.Module):
             x = x.contiguous(memory_format=torch.channels_last)
         return x
 
+    def _workspace(self, x):
+        if not x.is_cuda:
+            return None
+        if self._ws is None or self._ws[0].device != x.device:
+            # layouts match BN_GM_MAX=512 in csrc/ext.hip: reduce partials
+            # plus scale/shift (fwd) and k1..k3 (bwd). Only values that are
+            # dead when the call returns live here; save_mean/save_rstd come
+            # back freshly allocated, so calling this module twice before
+            # backward is safe.
+            self._ws = (
+                torch.empty(2 * 512 + 4, self.num_features, device=x.device),
+                torch.empty(2 * 512 + 3, self.num_features, device=x.device))
+        return self._ws
+
     def forward(self, x, residual: Optional[torch.Tensor] = None):
         x = self._check(x)
         if residual is not None:
             residual = self._check(residual)
         if self.training:
             self.num_batches_tracked += 1
-            if x.is_cuda and (self._ws is None
-                              or self._ws[0].device != x.device):
-                # layouts match BN_GM_MAX=512 in csrc/ext.hip: reduce
-                # partials plus scale/shift (fwd) and k1..k3 (bwd). Only
-                # values that are dead when the call returns live here;
-                # save_mean/save_rstd come back freshly allocated, so calling
-                # this module twice before backward is safe.
-                self._ws = (
-                    torch.empty(2 * 512 + 4, self.num_features,
-                                device=x.device),
-                    torch.empty(2 * 512 + 3, self.num_features,
-                                device=x.device))
             return fused_bn_train(x, self.weight, self.bias,
                                   self.running_mean, self.running_var,
                                   self.momentum, self.eps, self.relu, residual,
-                                  ws=self._ws if x.is_cuda else None)
+                                  ws=self._workspace(x))
         # eval: running-stat normalize (+add+relu)
         scale = self.weight * (self.running_var + self.eps).rsqrt()
         shift = self.bias - self.running_mean * scale
@@ -157,6 +221,45 @@ class FusedBatchNorm2d(torch.nn.Module):
 
     def forward_add(self, x, residual):
         return self.forward(x, residual)
+
+    def _fused_kernels(self, x):
+        return (self.training and x.is_cuda and ops_api.has_gpu_ops()
+                and not SPLIT_PATH)
+
+    def forward_pool(self, x):
+        """max_pool2d(self(x), 3, 2, 1), the ResNet stem, without the
+        full-resolution y: the apply kernel pools, backward gathers through
+        the saved argmax words. The caller uses this in place of
+        `pool(self(x))`, so forward hooks registered on this module (they
+        hang on `__call__`) do not fire."""
+        assert self.relu, "forward_pool is bn -> relu -> max-pool"
+        if not self._fused_kernels(x):
+            return torch.nn.functional.max_pool2d(self.forward(x), 3, 2, 1)
+        x = self._check(x)
+        self.num_batches_tracked += 1
+        return _FusedBNPoolFunction.apply(
+            x, self.weight, self.bias, self.running_mean, self.running_var,
+            self.momentum, self.eps, self._workspace(x))
+
+    def forward_add_bn(self, z, zd, other_bn):
+        """relu(self_bn(z) + other_bn(zd)): the tail of a block whose identity
+        branch ends in a ReLU-less BN (`other_bn`), with one apply kernel and
+        no stored identity tensor. `other_bn` is handed over, not called:
+        forward hooks on it, on this module and on a Sequential that holds
+        `other_bn` do not fire on this path."""
+        if not (self._fused_kernels(z) and self.relu
+                and isinstance(other_bn, FusedBatchNorm2d)
+                and other_bn.training and not other_bn.relu):
+            return self.forward_add(z, other_bn(zd))
+        z, zd = self._check(z), other_bn._check(zd)
+        self.num_batches_tracked += 1
+        other_bn.num_batches_tracked += 1
+        return _FusedBNAddBNFunction.apply(
+            z, zd, self.weight, self.bias, self.running_mean,
+            self.running_var, self.momentum, self.eps, self._workspace(z),
+            other_bn.weight, other_bn.bias, other_bn.running_mean,
+            other_bn.running_var, other_bn.momentum, other_bn.eps,
+            other_bn._workspace(zd))
 
     def extra_repr(self):
         return f"{self.num_features}, relu={self.relu}"

@@ -1,6 +1,6 @@
 """Microbenchmark of the fused BN kernels at the BN layers of ResNet-50.
 
-    python tools/bn_microbench.py [--batch 512] [--miopen] [--iters 20]
+    python tools/bn_microbench.py [--batch 512] [--miopen] [--iters 20] [--ab]
 
 Runs on a GPU. For every distinct BN layer of ResNet-50 (channels, spatial
 size, kind: relu / add+relu / plain, and how many such layers the network
@@ -12,6 +12,15 @@ by their count: per-step time, bytes moved (computed from the shapes) and the
 achieved rate of every family, so a change to one kernel can be judged
 without the full model. --miopen adds the wall-clock comparison against
 MIOpen BN + add + relu.
+
+Two kinds run more than one BN kernel chain: `pool` is the stem's
+bn -> relu -> 3x3/2 max-pool (FusedBatchNorm2d.forward_pool) and `add_bn` the
+tail of a block with a downsample, relu(bn3(z) + bn_ds(zd))
+(forward_add_bn, two BN layers). --ab times these five layers a second time
+through the split path they replace (bn -> F.max_pool2d; bn_ds, then bn3 with
+a residual), in the same build, and prints both per kernel family; torch's
+pool kernels and whatever else the split path launches (fills, copies) are
+counted there.
 
 Each layer rotates through enough input sets to exceed the 256 MiB Infinity
 Cache; one set timed in a loop would be read from cache, not from HBM.
@@ -28,25 +37,29 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 # (C, H = W, kind, layers of this kind in ResNet-50 v1.5): 53 in all,
 # 11.11 M elements per image
 LAYERS = [
-    (64, 112, "relu", 1),
-    (64, 56, "relu", 6), (256, 56, "add", 3), (256, 56, "plain", 1),
-    (128, 56, "relu", 1), (128, 28, "relu", 7), (512, 28, "add", 4),
-    (512, 28, "plain", 1),
-    (256, 28, "relu", 1), (256, 14, "relu", 11), (1024, 14, "add", 6),
-    (1024, 14, "plain", 1),
-    (512, 14, "relu", 1), (512, 7, "relu", 5), (2048, 7, "add", 3),
-    (2048, 7, "plain", 1),
+    (64, 112, "pool", 1),
+    (64, 56, "relu", 6), (256, 56, "add", 2), (256, 56, "add_bn", 1),
+    (128, 56, "relu", 1), (128, 28, "relu", 7), (512, 28, "add", 3),
+    (512, 28, "add_bn", 1),
+    (256, 28, "relu", 1), (256, 14, "relu", 11), (1024, 14, "add", 5),
+    (1024, 14, "add_bn", 1),
+    (512, 14, "relu", 1), (512, 7, "relu", 5), (2048, 7, "add", 2),
+    (2048, 7, "add_bn", 1),
 ]
-assert sum(n for *_, n in LAYERS) == 53
+BN_PER_KIND = {"relu": 1, "add": 1, "plain": 1, "pool": 1, "add_bn": 2}
+assert sum(n * BN_PER_KIND[k] for _, _, k, n in LAYERS) == 53
 
+# kernel families: our kernels by their name without "_kernel", torch's pool
+# kernels by theirs; "other" is every other kernel the timed call launched
 FAMILIES = ["bn_fwd_reduce", "bn_fwd_finalize", "bn_fwd_apply",
-            "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply"]
+            "bn_fwd_pool_apply", "bn_fwd_apply_add_bn",
+            "max_pool_forward_nhwc",
+            "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply",
+            "max_pool_backward_nhwc", "other"]
 ROTATE_BYTES = 1 << 30
 
 
-def family_bytes(kind, n_elem, C, gm_rows, has_mask):
-    """Bytes each kernel family has to move for one bf16 layer, from shapes.
-    With the packed mask, backward reads 1 bit where it read a bf16 y."""
+def _bn_bytes(kind, n_elem, C, gm_rows, has_mask):
     e = 2 * n_elem                      # one bf16 pass over the tensor
     mask = n_elem // 8 if (has_mask and kind != "plain") else 0
     # what backward reads for y > 0: nothing, the mask, or y itself
@@ -60,6 +73,65 @@ def family_bytes(kind, n_elem, C, gm_rows, has_mask):
         "bn_bwd_finalize": part,
         "bn_bwd_apply": e * (4 if kind == "add" else 3) + sign,
     }
+
+
+def family_bytes(kind, n_elem, C, gm_rows, has_mask, split=False):
+    """Bytes each kernel family has to move for one bf16 layer, from shapes
+    (n_elem: elements of the BN input). With the packed mask, backward reads
+    1 bit where it read a bf16 y. `other` kernels are not given bytes."""
+    out = dict.fromkeys(FAMILIES, 0)
+    e = 2 * n_elem
+    part = 2 * gm_rows * C * 4
+    if kind == "pool" and split:
+        out.update(_bn_bytes("relu", n_elem, C, gm_rows, has_mask))
+        # pooled y is a quarter; torch keeps int64 indices, 8 B per pooled
+        # element = one bf16 pass of the full tensor
+        out["max_pool_forward_nhwc"] = e + e // 4 + e
+        out["max_pool_backward_nhwc"] = e // 4 + e + e
+    elif kind == "pool":
+        words = n_elem // 8             # 4 B per 8 pooled channels
+        out.update({
+            "bn_fwd_reduce": e + part, "bn_fwd_finalize": part,
+            "bn_fwd_pool_apply": e + e // 4 + words,
+            "bn_bwd_reduce": e + e // 4 + words + part,
+            "bn_bwd_finalize": part,
+            "bn_bwd_apply": e + e // 4 + words + e,
+        })
+    elif kind == "add_bn" and split:
+        a = _bn_bytes("add", n_elem, C, gm_rows, has_mask)
+        b = _bn_bytes("plain", n_elem, C, gm_rows, has_mask)
+        out.update({f: a[f] + b[f] for f in a})
+    elif kind == "add_bn":
+        mask = n_elem // 8
+        out.update({
+            "bn_fwd_reduce": 2 * (e + part), "bn_fwd_finalize": 2 * part,
+            "bn_fwd_apply_add_bn": 3 * e + mask,
+            "bn_bwd_reduce": 2 * (2 * e + mask + part),
+            "bn_bwd_finalize": 2 * part,
+            "bn_bwd_apply": 2 * (3 * e + mask),
+        })
+    else:
+        out.update(_bn_bytes(kind, n_elem, C, gm_rows, has_mask))
+    return out
+
+
+def expected_launches(kind, split):
+    """Launches of each of our families (and torch's pool kernels) in one
+    forward+backward of a layer; `other` is not checked."""
+    n = dict.fromkeys(FAMILIES, 0)
+    two = 2 if kind == "add_bn" else 1
+    for f in ("bn_fwd_reduce", "bn_fwd_finalize", "bn_bwd_reduce",
+              "bn_bwd_finalize", "bn_bwd_apply"):
+        n[f] = two
+    if kind == "pool" and not split:
+        n["bn_fwd_pool_apply"] = 1
+    elif kind == "add_bn" and not split:
+        n["bn_fwd_apply_add_bn"] = 1
+    else:
+        n["bn_fwd_apply"] = two
+        if kind == "pool":
+            n["max_pool_forward_nhwc"] = n["max_pool_backward_nhwc"] = 1
+    return n
 
 
 def reduce_gm(M, C):
@@ -80,8 +152,8 @@ def time_fn(fn, iters, warm=3):
     return (time.perf_counter() - t0) / iters * 1e3
 
 
-def kernel_times(fn, iters):
-    """us per call of every BN kernel family over `iters` calls of fn."""
+def kernel_times(fn, iters, expect):
+    """us per call of every kernel family over `iters` calls of fn."""
     from torch.profiler import ProfilerActivity, profile
     for _ in range(3):
         fn()
@@ -93,17 +165,21 @@ def kernel_times(fn, iters):
     out = dict.fromkeys(FAMILIES, 0.0)
     seen = dict.fromkeys(FAMILIES, 0)
     for ev in prof.key_averages():
-        for fam in FAMILIES:
-            if fam + "_kernel" in ev.key:
-                t = getattr(ev, "device_time_total", None)
-                if t is None:
-                    t = ev.cuda_time_total
-                out[fam] += t / iters
-                seen[fam] += ev.count
-    missing = [f for f in FAMILIES if seen[f] != iters]
-    if missing:
-        raise RuntimeError(f"profiler recorded {seen}, expected {iters} "
-                           f"launches of each BN kernel")
+        t = getattr(ev, "device_time_total", None)
+        if t is None:
+            t = ev.cuda_time_total
+        if not t:
+            continue
+        fam = next((f for f in FAMILIES
+                    if (f + "_kernel" if f.startswith("bn_") else f)
+                    in ev.key), "other")
+        out[fam] += t / iters
+        seen[fam] += ev.count
+    wrong = {f: seen[f] for f in FAMILIES
+             if f != "other" and seen[f] != iters * expect[f]}
+    if wrong:
+        raise RuntimeError(f"profiler recorded {wrong}, expected {iters} x "
+                           f"{expect}")
     return out
 
 
@@ -114,28 +190,38 @@ def main():
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--miopen", action="store_true",
                     help="also time MIOpen BN + add + relu (wall clock)")
+    ap.add_argument("--ab", action="store_true",
+                    help="time the pool / add_bn layers through the split "
+                         "path as well and print both")
     args = ap.parse_args()
 
-    from autodist_amd.ops import api
-    from autodist_amd.ops.fused_bn import fused_bn_train
+    from autodist_amd.ops import api, fused_bn
+    from autodist_amd.ops.fused_bn import FusedBatchNorm2d, fused_bn_train
     has_mask = hasattr(api.ext(), "bn_fwd_train_mask")
     dev = torch.device("cuda")
     N = args.batch
     print(f"# batch {N}, bf16, packed ReLU mask: {has_mask}; us per call")
     print(f"{'C':>5} {'HW':>4} {'kind':>5} {'x':>3} "
-          + " ".join(f"{f[3:]:>13}" for f in FAMILIES)
+          + " ".join(f"{f[3:] if f.startswith('bn_') else f[:13]:>13}"
+                     for f in FAMILIES)
           + (f" {'fusedFB':>9} {'miopenFB':>9}" if args.miopen else ""))
     step_us = dict.fromkeys(FAMILIES, 0.0)
     step_bytes = dict.fromkeys(FAMILIES, 0)
+    # the pool / add_bn layers, fused and (--ab) split: kind -> path -> sums
+    ab_us = {k: {p: dict.fromkeys(FAMILIES, 0.0) for p in ("fused", "split")}
+             for k in ("pool", "add_bn")}
+    ab_bytes = {k: {p: dict.fromkeys(FAMILIES, 0) for p in ("fused", "split")}
+                for k in ("pool", "add_bn")}
     for (C, HW, kind, count) in LAYERS:
         n_elem = N * C * HW * HW
         sets = max(2, min(16, ROTATE_BYTES // (2 * n_elem)))
-        mk = lambda: torch.randn(N, C, HW, HW, device=dev,  # noqa: E731
-                                 dtype=torch.bfloat16).contiguous(
-                                     memory_format=torch.channels_last)
+        mk = lambda hw=HW: torch.randn(N, C, hw, hw, device=dev,  # noqa: E731
+                                       dtype=torch.bfloat16).contiguous(
+                                           memory_format=torch.channels_last)
         xs = [mk() for _ in range(sets)]
-        rs = [mk() for _ in range(sets)] if kind == "add" else None
-        gs = [mk() for _ in range(sets)]
+        rs = [mk() for _ in range(sets)] if kind in ("add", "add_bn") else None
+        gs = [mk((HW - 1) // 2 + 1 if kind == "pool" else HW)
+              for _ in range(sets)]
         w = torch.nn.Parameter(torch.rand(C, device=dev) + 0.5)
         b = torch.nn.Parameter(torch.randn(C, device=dev))
         rm, rv = torch.zeros(C, device=dev), torch.ones(C, device=dev)
@@ -143,20 +229,44 @@ def main():
               torch.empty(2 * 512 + 3, C, device=dev))
         turn = [0]
 
+        bn = FusedBatchNorm2d(C, relu=True).to(dev).train()
+        bn_d = FusedBatchNorm2d(C, relu=False).to(dev).train()
+
         def fused_fwd_bwd():
             i = turn[0] = (turn[0] + 1) % sets
             xg = xs[i].detach().requires_grad_(True)
             rg = rs[i].detach().requires_grad_(True) if rs else None
-            y = fused_bn_train(xg, w, b, rm, rv, relu=kind != "plain",
-                               residual=rg, ws=ws)
+            if kind == "pool":
+                y = bn.forward_pool(xg)
+            elif kind == "add_bn":
+                y = bn.forward_add_bn(xg, rg, bn_d)
+            else:
+                y = fused_bn_train(xg, w, b, rm, rv, relu=kind != "plain",
+                                   residual=rg, ws=ws)
             y.backward(gs[i])
 
-        kt = kernel_times(fused_fwd_bwd, args.iters)
-        fb = family_bytes(kind, n_elem, C, reduce_gm(N * HW * HW, C),
-                          has_mask)
+        gm = reduce_gm(N * HW * HW, C)
+        kt = kernel_times(fused_fwd_bwd, args.iters,
+                          expected_launches(kind, False))
+        fb = family_bytes(kind, n_elem, C, gm, has_mask)
         for f in FAMILIES:
             step_us[f] += count * kt[f]
             step_bytes[f] += count * fb[f]
+        if kind in ab_us:
+            paths = [("fused", kt, fb)]
+            if args.ab:
+                fused_bn.SPLIT_PATH = True
+                try:
+                    paths.append(("split", kernel_times(
+                        fused_fwd_bwd, args.iters,
+                        expected_launches(kind, True)),
+                        family_bytes(kind, n_elem, C, gm, has_mask, True)))
+                finally:
+                    fused_bn.SPLIT_PATH = False
+            for path, t, nb in paths:
+                for f in FAMILIES:
+                    ab_us[kind][path][f] += count * t[f]
+                    ab_bytes[kind][path][f] += count * nb[f]
         line = (f"{C:5d} {HW:4d} {kind:>5} {count:3d} "
                 + " ".join(f"{kt[f]:13.1f}" for f in FAMILIES))
         if args.miopen:
@@ -179,12 +289,33 @@ def main():
         del xs, rs, gs
 
     print(f"# per training step (53 layers, batch {N}), bytes from shapes")
-    print(f"{'family':>16} {'ms/step':>9} {'GB/step':>9} {'TB/s':>7}")
+    print(f"{'family':>24} {'ms/step':>9} {'GB/step':>9} {'TB/s':>7}")
     for f in FAMILIES:
         ms, gb = step_us[f] / 1e3, step_bytes[f] / 1e9
-        print(f"{f:>16} {ms:9.3f} {gb:9.2f} {gb / ms:7.2f}")
-    print(f"{'all BN kernels':>16} {sum(step_us.values()) / 1e3:9.3f} "
+        rate = f"{gb / ms:7.2f}" if ms and gb else f"{'-':>7}"
+        print(f"{f:>24} {ms:9.3f} {gb:9.2f} {rate}")
+    print(f"{'all kernels above':>24} {sum(step_us.values()) / 1e3:9.3f} "
           f"{sum(step_bytes.values()) / 1e9:9.2f}")
+    if not args.ab:
+        return
+    for kind, what in (("pool", "the stem layer"),
+                       ("add_bn", "the four downsample tails")):
+        print(f"# {kind}: {what}, per training step, split path | fused")
+        print(f"{'family':>24} {'ms':>8} {'GB':>7} {'TB/s':>6} | "
+              f"{'ms':>8} {'GB':>7} {'TB/s':>6}")
+        for f in FAMILIES:
+            cells = []
+            for path in ("split", "fused"):
+                ms = ab_us[kind][path][f] / 1e3
+                gb = ab_bytes[kind][path][f] / 1e9
+                rate = f"{gb / ms:6.2f}" if ms and gb else f"{'-':>6}"
+                cells.append(f"{ms:8.3f} {gb:7.2f} {rate}")
+            print(f"{f:>24} " + " | ".join(cells))
+        tot = [sum(ab_us[kind][p].values()) / 1e3 for p in ("split", "fused")]
+        gbs = [sum(ab_bytes[kind][p].values()) / 1e9
+               for p in ("split", "fused")]
+        print(f"{'sum':>24} {tot[0]:8.3f} {gbs[0]:7.2f} {'':>6} | "
+              f"{tot[1]:8.3f} {gbs[1]:7.2f}")
 
 
 if __name__ == "__main__":
