@@ -38,16 +38,24 @@ class Bottleneck(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
 
+    def forward_pair(self, xs):
+        """Fused path, block input and output as (main, res): two handles of
+        one tensor, conv1 reads the first and the residual (or the downsample
+        conv) the second, so the tail before this block gets their gradients
+        apart (FusedBatchNorm2d.forward_add_pair)."""
+        x_main, x_res = xs
+        out = self.bn1(self.conv1(x_main))
+        out = self.bn2(self.conv2(out))
+        z = self.conv3(out)
+        if self.downsample is None:
+            return self.bn3.forward_add_pair(z, x_res)
+        # downsample = (conv, ReLU-less bn): its bn joins bn3's kernel
+        return self.bn3.forward_add_bn_pair(z, self.downsample[0](x_res),
+                                            self.downsample[1])
+
     def forward(self, x):
         if self.fused:
-            out = self.bn1(self.conv1(x))
-            out = self.bn2(self.conv2(out))
-            z = self.conv3(out)
-            if self.downsample is None:
-                return self.bn3.forward_add(z, x)
-            # downsample = (conv, ReLU-less bn): its bn joins bn3's kernel
-            return self.bn3.forward_add_bn(z, self.downsample[0](x),
-                                           self.downsample[1])
+            return self.forward_pair((x, x))[0]
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
@@ -71,14 +79,19 @@ class BasicBlock(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
 
+    def forward_pair(self, xs):
+        """See Bottleneck.forward_pair."""
+        x_main, x_res = xs
+        out = self.bn1(self.conv1(x_main))
+        z = self.conv2(out)
+        if self.downsample is None:
+            return self.bn2.forward_add_pair(z, x_res)
+        return self.bn2.forward_add_bn_pair(z, self.downsample[0](x_res),
+                                            self.downsample[1])
+
     def forward(self, x):
         if self.fused:
-            out = self.bn1(self.conv1(x))
-            z = self.conv2(out)
-            if self.downsample is None:
-                return self.bn2.forward_add(z, x)
-            return self.bn2.forward_add_bn(z, self.downsample[0](x),
-                                           self.downsample[1])
+            return self.forward_pair((x, x))[0]
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
@@ -130,9 +143,18 @@ class ResNet(nn.Module):
             # bn -> relu -> maxpool in the BN kernels; self.maxpool stays for
             # the unfused path and the module structure
             x = self.bn1.forward_pool(self.conv1(x))
+            # the blocks are walked here and chained by forward_pair, so that
+            # every block input but the first reaches its two consumers as two
+            # handles. Forward hooks on the blocks and on the layerN
+            # Sequentials (they hang on `__call__`) do not fire on this path.
+            xs = (x, x)
+            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+                for block in layer:
+                    xs = block.forward_pair(xs)
+            x = xs[0]
         else:
             x = self.maxpool(self.relu(self.bn1(self.conv1(x))))
-        x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
+            x = self.layer4(self.layer3(self.layer2(self.layer1(x))))
         x = self.avgpool(x).flatten(1)
         return self.fc(x)
 

@@ -616,6 +616,114 @@ bn_bwd_reduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
   }
 }
 
+// ----------------------------------------------- bwd reduce, two gradients
+// The tail of a residual block gets its dy as two addends (the block output
+// feeds the next block's conv1 and its residual / downsample conv). This is
+// the BN_RELU_MASK reduce with the add folded in:
+//   dz = bit ? T(float(a) + float(b)) : 0
+// one fp32 add rounded to T, which is torch's a + b, then the mask. The sums
+// are taken from the rounded, masked value with the expressions and in the
+// order of bn_bwd_reduce_kernel, so the partial rows are those of that kernel
+// on dy = a + b. dz is stored: it is the dres of the split path, and
+// bn_bwd_apply_kernel<T, BN_RELU_NONE, false> on dy = dz gives its dx.
+// BN_JOIN_U rows in flight: 3 streams of 16 B and the mask byte per row.
+#ifndef BN_JOIN_U
+#define BN_JOIN_U 4
+#endif
+template <typename T>
+__device__ __forceinline__ void bn_join_dz8(const float* av, const float* bv,
+                                            unsigned bits, float* dv) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k)
+    dv[k] = (bits >> k) & 1u ? round_to(av[k] + bv[k], (const T*)nullptr)
+                             : 0.f;
+}
+
+template <typename T>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+__attribute__((amdgpu_waves_per_eu(1)))
+bn_bwd_reduce_join_kernel(const T* __restrict__ x, const T* __restrict__ dy_a,
+                          const T* __restrict__ dy_b,
+                          const unsigned char* __restrict__ mask,
+                          const float* __restrict__ save_mean,
+                          const float* __restrict__ save_rstd,
+                          float* __restrict__ partial_dz,
+                          float* __restrict__ partial_dzxh,
+                          T* __restrict__ dz, long M, int C) {
+#pragma clang fp contract(off)  // see bn_fwd_reduce_kernel
+  int tx_count = min(C / BN_VEC, (int)blockDim.x);
+  int tx = threadIdx.x % tx_count;
+  int ty = threadIdx.x / tx_count;
+  int rows_per_blk = blockDim.x / tx_count;
+  int c0 = (blockIdx.y * tx_count + tx) * BN_VEC;
+  if (c0 >= C) return;
+  float mean[BN_VEC], rstd[BN_VEC];
+  load8(save_mean + c0, mean);
+  load8(save_rstd + c0, rstd);
+  float s[BN_VEC] = {0}, t[BN_VEC] = {0};
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  for (; m + (BN_JOIN_U - 1) * stride < M; m += BN_JOIN_U * stride) {
+    Raw8<T> rx[BN_JOIN_U], ra[BN_JOIN_U], rb[BN_JOIN_U];
+    unsigned rm[BN_JOIN_U];
+#pragma unroll
+    for (int u = 0; u < BN_JOIN_U; ++u) {
+      const long mu = m + u * stride;
+      rx[u] = load8raw(x + mu * C + c0);
+      ra[u] = load8raw(dy_a + mu * C + c0);
+      rb[u] = load8raw(dy_b + mu * C + c0);
+      rm[u] = mask[mu * (C / BN_VEC) + c0 / BN_VEC];
+    }
+    // every load of the trip is issued before the first row is consumed
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < BN_JOIN_U; ++u) {
+      float xv[BN_VEC], av[BN_VEC], bv[BN_VEC], dv[BN_VEC];
+      unpack8(rx[u], xv);
+      unpack8(ra[u], av);
+      unpack8(rb[u], bv);
+      bn_join_dz8<T>(av, bv, rm[u], dv);
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) {
+        s[k] += dv[k];
+        t[k] = fmaf(dv[k] * (xv[k] - mean[k]), rstd[k], t[k]);
+      }
+      store8(dz + (m + u * stride) * C + c0, dv);
+    }
+  }
+  for (; m < M; m += stride) {
+    float xv[BN_VEC], av[BN_VEC], bv[BN_VEC], dv[BN_VEC];
+    load8(x + m * C + c0, xv);
+    load8(dy_a + m * C + c0, av);
+    load8(dy_b + m * C + c0, bv);
+    bn_join_dz8<T>(av, bv, mask[m * (C / BN_VEC) + c0 / BN_VEC], dv);
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) {
+      s[k] += dv[k];
+      t[k] = fmaf(dv[k] * (xv[k] - mean[k]), rstd[k], t[k]);
+    }
+    store8(dz + m * C + c0, dv);
+  }
+  __shared__ float ls[BLOCK_THREADS * BN_VEC];
+  __shared__ float lt[BLOCK_THREADS * BN_VEC];
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) {
+    ls[threadIdx.x * BN_VEC + k] = s[k];
+    lt[threadIdx.x * BN_VEC + k] = t[k];
+  }
+  __syncthreads();
+  if (ty == 0) {
+    for (int r = 1; r < rows_per_blk; ++r) {
+      int o = (r * tx_count + tx) * BN_VEC;
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) { s[k] += ls[o + k]; t[k] += lt[o + k]; }
+    }
+    store8(partial_dz + (long)blockIdx.x * C + c0, s);
+    store8(partial_dzxh + (long)blockIdx.x * C + c0, t);
+  }
+}
+
 // ------------------------------------------------------------ bwd finalize
 // k1 = w*rstd ; k2 = sum_dz/M ; k3 = sum_dzxh/M ; dweight = sum_dzxh ;
 // dbias = sum_dz

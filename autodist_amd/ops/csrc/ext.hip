@@ -441,6 +441,84 @@ std::vector<torch::Tensor> bn_bwd_mask(torch::Tensor x, torch::Tensor dy,
                                        weight, need_dres, ws);
 }
 
+// bn_bwd_mask for a dy that arrives as two addends: the join reduce forms
+// dz = mask ? T(dy_a + dy_b) : 0 and stores it, the finalize is the usual
+// one, and the plain apply runs on dy = dz. Returns (dx, dweight, dbias, dz);
+// dz is what bn_bwd_mask(need_dres) returns as dres for dy = dy_a + dy_b.
+template <typename T>
+std::vector<torch::Tensor> bn_bwd_mask_join_impl(
+    const torch::Tensor& x, const torch::Tensor& dy_a,
+    const torch::Tensor& dy_b, const torch::Tensor& mask,
+    const torch::Tensor& save_mean, const torch::Tensor& save_rstd,
+    const torch::Tensor& weight, const c10::optional<torch::Tensor>& ws) {
+  // ws rows as in bn_bwd_impl
+  auto g = bn_geom(x);
+  for (const torch::Tensor* d : {&dy_a, &dy_b})
+    TORCH_CHECK(d->sizes() == x.sizes() &&
+                    d->scalar_type() == x.scalar_type() &&
+                    d->device() == x.device() &&
+                    d->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "bn_bwd_mask_join: dy_a and dy_b must match x in shape, "
+                "dtype, device and channels_last layout");
+  auto fopt = weight.options().dtype(torch::kFloat32);
+  torch::Tensor w5 = ws.has_value() ? *ws
+      : torch::empty({2 * BN_GM_MAX + 3, (long)g.C}, fopt);
+  TORCH_CHECK(w5.size(0) >= 2 * BN_GM_MAX + 3 && w5.size(1) == g.C &&
+              w5.is_contiguous());
+  TORCH_CHECK(mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
+                  mask.dim() == 2 && mask.size(0) == g.M &&
+                  mask.size(1) == g.C / BN_VEC && mask.device() == x.device(),
+              "mask must be the [M, C/8] uint8 tensor of bn_fwd_train_mask");
+  const unsigned char* mp = mask.data_ptr<unsigned char>();
+  float* wp = w5.data_ptr<float>();
+  float* partial_dz = wp;
+  float* partial_dzxh = wp + (long)BN_GM_MAX * g.C;
+  float* k1 = wp + (long)(2 * BN_GM_MAX + 0) * g.C;
+  float* k2 = wp + (long)(2 * BN_GM_MAX + 1) * g.C;
+  float* k3 = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
+  auto dweight = torch::empty({g.C}, fopt);
+  auto dbias = torch::empty({g.C}, fopt);
+  auto dx = torch::empty_like(x);
+  auto dz = torch::empty_like(x);
+  dim3 block(BLOCK_THREADS);
+  int gm = bn_reduce_gm(g);
+  dim3 grid_r(gm, g.grid_c);
+  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  auto st = cur_stream();
+  const float* sm = save_mean.data_ptr<float>();
+  const float* sr = save_rstd.data_ptr<float>();
+
+  hipLaunchKernelGGL((bn_bwd_reduce_join_kernel<T>), grid_r, block, 0, st,
+                     bn_ptr<const T>(x), bn_ptr<const T>(dy_a),
+                     bn_ptr<const T>(dy_b), mp, sm, sr, partial_dz,
+                     partial_dzxh, bn_ptr<T>(dz), g.M, g.C);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel,
+                     dim3((g.C + FIN_CH - 1) / FIN_CH),
+                     dim3(FIN_CH * FIN_LANES), 0, st, partial_dz,
+                     partial_dzxh, gm, weight.data_ptr<float>(), sr, k1, k2,
+                     k3, dweight.data_ptr<float>(), dbias.data_ptr<float>(),
+                     g.M, g.C);
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, BN_RELU_NONE, false>), grid_a,
+                     block, 0, st, bn_ptr<const T>(x), bn_ptr<const T>(dz),
+                     (const T*)nullptr, (const unsigned char*)nullptr, sm, sr,
+                     k1, k2, k3, bn_ptr<T>(dx), (T*)nullptr, g.M, g.C,
+                     BNPool{});
+  return {dx, dweight, dbias, dz};
+}
+
+std::vector<torch::Tensor> bn_bwd_mask_join(
+    torch::Tensor x, torch::Tensor dy_a, torch::Tensor dy_b,
+    torch::Tensor mask, torch::Tensor save_mean, torch::Tensor save_rstd,
+    torch::Tensor weight, c10::optional<torch::Tensor> ws) {
+  if (x.scalar_type() == torch::kBFloat16)
+    return bn_bwd_mask_join_impl<__hip_bfloat16>(x, dy_a, dy_b, mask,
+                                                 save_mean, save_rstd, weight,
+                                                 ws);
+  TORCH_CHECK(x.scalar_type() == torch::kFloat32);
+  return bn_bwd_mask_join_impl<float>(x, dy_a, dy_b, mask, save_mean,
+                                      save_rstd, weight, ws);
+}
+
 // bn_bwd for bn_fwd_train_pool: dy is the pooled dy, argmax the forward's
 // argmax words; the kernels gather dz through them (BN_RELU_POOL).
 // -> (dx, dweight, dbias)
@@ -1227,6 +1305,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("bn_bwd_mask", &bn_bwd_mask,
         "bn_bwd that takes the packed mask of bn_fwd_train_mask in place of "
         "y");
+  m.def("bn_bwd_mask_join", &bn_bwd_mask_join,
+        "bn_bwd_mask for dy = dy_a + dy_b, the add done in the reduce: (x, "
+        "dy_a, dy_b, mask, save_mean, save_rstd, weight, ws) -> (dx, "
+        "dweight, dbias, dz); dz is the masked sum, the split path's dres");
   m.def("bn_fwd_train_pool", &bn_fwd_train_pool,
         "bn + relu + 3x3/stride 2/pad 1 max-pool: (x, weight, bias, "
         "running_mean, running_var, eps, momentum, ws) -> (pooled y, "
@@ -1241,6 +1323,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // rows in flight per thread in the BN reduce / finalize loops
   m.attr("BN_RED_U") = BN_RED_U;
   m.attr("BN_FIN_U") = BN_FIN_U;
+  m.attr("BN_JOIN_U") = BN_JOIN_U;
   m.def("psgd_mq", &psgd_mq, "PowerSGD P = M @ Q (MFMA f32 16x16x4)");
   m.def("psgd_mtp", &psgd_mtp, "PowerSGD Qn = M^T @ P (MFMA f32 16x16x4)");
   m.def("psgd_decompress_ef", &psgd_decompress_ef,

@@ -20,16 +20,31 @@ from autodist_amd.ops import api as ops_api
 
 
 # True routes forward_pool / forward_add_bn through the separate kernels they
-# replace (bn -> F.max_pool2d, bn_ds -> bn.forward_add): the A/B switch of
-# tools/bn_microbench.py and the reference of the GPU tests.
+# replace (bn -> F.max_pool2d, bn_ds -> bn.forward_add) and makes the *_pair
+# tails return one tensor twice, so that autograd adds the two gradients
+# itself: the A/B switch of tools/bn_microbench.py and the reference of the
+# GPU tests.
 SPLIT_PATH = False
+
+
+def _two_handles(ctx, y):
+    """(y, a view of y): autograd hands backward the gradient of each handle
+    on its own instead of their sum, and None for a handle nobody used."""
+    ctx.set_materialize_grads(False)
+    return y, y.view_as(y)
+
+
+def _nhwc_grad(g):
+    return None if g is None else g.contiguous(
+        memory_format=torch.channels_last)
 
 
 class _FusedBNFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var,
-                momentum, eps, relu, residual, ws=None):
+                momentum, eps, relu, residual, ws=None, pair=False):
         use_hip = x.is_cuda and ops_api.has_gpu_ops()
+        assert not pair or (use_hip and relu and residual is not None)
         ctx.ws_bwd = ws[1] if ws is not None else None
         if use_hip and relu:
             # backward needs y only for its sign: the apply kernel packs
@@ -70,15 +85,25 @@ class _FusedBNFunction(torch.autograd.Function):
         ctx.save_for_backward(x, sign, save_mean, save_rstd, weight)
         ctx.relu = relu
         ctx.has_res = residual is not None
-        return y
+        return _two_handles(ctx, y) if pair else y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy_b=None):
         # sign: y itself, or on the HIP path with relu its packed y > 0 mask
         x, sign, save_mean, save_rstd, weight = ctx.saved_tensors
         relu, has_res = ctx.relu, ctx.has_res
         use_hip = x.is_cuda and ops_api.has_gpu_ops()
-        if use_hip:
+        if dy is None:  # pair: only the second handle was used, or neither
+            dy, dy_b = dy_b, None
+            if dy is None:
+                return (None,) * 11
+        if dy_b is not None:
+            # pair, both handles used: the add happens in the reduce kernel,
+            # and its masked sum dz is the residual's gradient
+            dx, dweight, dbias, dres = ops_api.ext().bn_bwd_mask_join(
+                x, _nhwc_grad(dy), _nhwc_grad(dy_b), sign, save_mean,
+                save_rstd, weight, ctx.ws_bwd)
+        elif use_hip:
             bwd = ops_api.ext().bn_bwd_mask if relu else ops_api.ext().bn_bwd
             out = bwd(x, dy.contiguous(
                 memory_format=torch.channels_last), sign, save_mean, save_rstd,
@@ -94,7 +119,8 @@ class _FusedBNFunction(torch.autograd.Function):
                 dyf, x.float(), weight, None, None, save_mean, save_rstd,
                 True, 0.0, [True, True, True])
             dx = dxf.to(x.dtype)
-        return (dx, dweight, dbias, None, None, None, None, None, dres, None)
+        return (dx, dweight, dbias, None, None, None, None, None, dres, None,
+                None)
 
 
 class _FusedBNPoolFunction(torch.autograd.Function):
@@ -122,12 +148,14 @@ class _FusedBNPoolFunction(torch.autograd.Function):
 
 class _FusedBNAddBNFunction(torch.autograd.Function):
     """relu(bn(z) + bn_d(zd)) with one apply kernel; backward is bn_bwd_mask
-    on each branch, both with the dy and the packed mask of y."""
+    on each branch, both with the dy and the packed mask of y. With `pair`
+    and both handles used, bn_bwd_mask_join on z adds the two gradients and
+    leaves the masked sum for a mask-less bn_bwd on zd."""
 
     @staticmethod
     def forward(ctx, z, zd, weight, bias, running_mean, running_var, momentum,
                 eps, ws, weight_d, bias_d, running_mean_d, running_var_d,
-                momentum_d, eps_d, ws_d):
+                momentum_d, eps_d, ws_d, pair=False):
         y, mask, sm, sr, sm_d, sr_d = ops_api.ext().bn_fwd_train_add_bn(
             z, zd, weight, bias, running_mean, running_var, eps, momentum,
             ws[0] if ws is not None else None,
@@ -137,25 +165,41 @@ class _FusedBNAddBNFunction(torch.autograd.Function):
         ctx.ws_bwd_d = ws_d[1] if ws_d is not None else None
         ctx.save_for_backward(z, zd, mask, sm, sr, sm_d, sr_d, weight,
                               weight_d)
-        return y
+        return _two_handles(ctx, y) if pair else y
 
     @staticmethod
-    def backward(ctx, dy):
+    def backward(ctx, dy, dy_b=None):
         z, zd, mask, sm, sr, sm_d, sr_d, weight, weight_d = ctx.saved_tensors
-        dy = dy.contiguous(memory_format=torch.channels_last)
-        bwd = ops_api.ext().bn_bwd_mask
-        dz, dw, db = bwd(z, dy, mask, sm, sr, weight, True, False, ctx.ws_bwd)
-        dzd, dw_d, db_d = bwd(zd, dy, mask, sm_d, sr_d, weight_d, True, False,
-                              ctx.ws_bwd_d)
+        if dy is None:  # pair: only the second handle was used, or neither
+            dy, dy_b = dy_b, None
+            if dy is None:
+                return (None,) * 17
+        dy = _nhwc_grad(dy)
+        if dy_b is not None:
+            dz, dw, db, dym = ops_api.ext().bn_bwd_mask_join(
+                z, dy, _nhwc_grad(dy_b), mask, sm, sr, weight, ctx.ws_bwd)
+            # dym is masked already; y is not read when relu is off
+            dzd, dw_d, db_d = ops_api.ext().bn_bwd(
+                zd, dym, dym, sm_d, sr_d, weight_d, False, False,
+                ctx.ws_bwd_d)
+        else:
+            bwd = ops_api.ext().bn_bwd_mask
+            dz, dw, db = bwd(z, dy, mask, sm, sr, weight, True, False,
+                             ctx.ws_bwd)
+            dzd, dw_d, db_d = bwd(zd, dy, mask, sm_d, sr_d, weight_d, True,
+                                  False, ctx.ws_bwd_d)
         return (dz, dzd, dw, db, None, None, None, None, None,
-                dw_d, db_d, None, None, None, None, None)
+                dw_d, db_d, None, None, None, None, None, None)
 
 
 def fused_bn_train(x, weight, bias, running_mean, running_var,
                    momentum=0.1, eps=1e-5, relu=False,
-                   residual: Optional[torch.Tensor] = None, ws=None):
+                   residual: Optional[torch.Tensor] = None, ws=None,
+                   pair=False):
+    """pair (HIP, relu and a residual only): returns two handles of y, see
+    FusedBatchNorm2d.forward_add_pair."""
     return _FusedBNFunction.apply(x, weight, bias, running_mean, running_var,
-                                  momentum, eps, relu, residual, ws)
+                                  momentum, eps, relu, residual, ws, pair)
 
 
 class FusedBatchNorm2d(torch.nn.Module):
@@ -165,6 +209,13 @@ class FusedBatchNorm2d(torch.nn.Module):
     bn(x) + residual -> relu (the Bottleneck tail); forward_pool(x) applies
     bn -> relu -> 3x3/2 max-pool (the ResNet stem); forward_add_bn(z, zd, bn_d)
     applies relu(bn(z) + bn_d(zd)) (the tail of a block with a downsample).
+
+    forward_add_pair / forward_add_bn_pair are the two tails for a block
+    output with two consumers: they return (y_main, y_res), two handles of
+    the one y. Give each consumer its own handle and backward receives the
+    two gradients apart and adds them inside its reduce kernel
+    (bn_bwd_mask_join) instead of reading a sum that a stand-alone add wrote.
+    Off the fused HIP path both handles are the same tensor and autograd adds.
     """
 
     def __init__(self, num_features, eps=1e-5, momentum=0.1, relu=False):
@@ -226,6 +277,18 @@ class FusedBatchNorm2d(torch.nn.Module):
         return (self.training and x.is_cuda and ops_api.has_gpu_ops()
                 and not SPLIT_PATH)
 
+    def forward_add_pair(self, x, residual):
+        """forward_add(x, residual) as (y_main, y_res)."""
+        if not (self._fused_kernels(x) and self.relu):
+            y = self.forward_add(x, residual)
+            return y, y
+        self.num_batches_tracked += 1
+        return fused_bn_train(self._check(x), self.weight, self.bias,
+                              self.running_mean, self.running_var,
+                              self.momentum, self.eps, True,
+                              self._check(residual), ws=self._workspace(x),
+                              pair=True)
+
     def forward_pool(self, x):
         """max_pool2d(self(x), 3, 2, 1), the ResNet stem, without the
         full-resolution y: the apply kernel pools, backward gathers through
@@ -241,7 +304,11 @@ class FusedBatchNorm2d(torch.nn.Module):
             x, self.weight, self.bias, self.running_mean, self.running_var,
             self.momentum, self.eps, self._workspace(x))
 
-    def forward_add_bn(self, z, zd, other_bn):
+    def forward_add_bn_pair(self, z, zd, other_bn):
+        """forward_add_bn(z, zd, other_bn) as (y_main, y_res)."""
+        return self.forward_add_bn(z, zd, other_bn, pair=True)
+
+    def forward_add_bn(self, z, zd, other_bn, pair=False):
         """relu(self_bn(z) + other_bn(zd)): the tail of a block whose identity
         branch ends in a ReLU-less BN (`other_bn`), with one apply kernel and
         no stored identity tensor. `other_bn` is handed over, not called:
@@ -250,7 +317,8 @@ class FusedBatchNorm2d(torch.nn.Module):
         if not (self._fused_kernels(z) and self.relu
                 and isinstance(other_bn, FusedBatchNorm2d)
                 and other_bn.training and not other_bn.relu):
-            return self.forward_add(z, other_bn(zd))
+            y = self.forward_add(z, other_bn(zd))
+            return (y, y) if pair else y
         z, zd = self._check(z), other_bn._check(zd)
         self.num_batches_tracked += 1
         other_bn.num_batches_tracked += 1
@@ -259,7 +327,7 @@ class FusedBatchNorm2d(torch.nn.Module):
             self.running_var, self.momentum, self.eps, self._workspace(z),
             other_bn.weight, other_bn.bias, other_bn.running_mean,
             other_bn.running_var, other_bn.momentum, other_bn.eps,
-            other_bn._workspace(zd))
+            other_bn._workspace(zd), pair)
 
     def extra_repr(self):
         return f"{self.num_features}, relu={self.relu}"

@@ -22,6 +22,15 @@ a residual), in the same build, and prints both per kernel family; torch's
 pool kernels and whatever else the split path launches (fills, copies) are
 counted there.
 
+--ab also times the `add` and `add_bn` tails with the block-output gradient
+arriving as two addends, as it does inside the network ("join"): once through
+the two-handle tails (forward_add_pair / forward_add_bn_pair: the add happens
+in bn_bwd_reduce_join, the apply reads its dz) and once through the
+single-handle tails, where autograd adds the two gradients with a stand-alone
+kernel first and backward is bn_bwd_mask (with dres for `add`). The last
+table weights these by the 15 block boundaries of ResNet-50 that have two
+consumers (every tail but layer4's last).
+
 Each layer rotates through enough input sets to exceed the 256 MiB Infinity
 Cache; one set timed in a loop would be read from cache, not from HBM.
 """
@@ -49,13 +58,16 @@ LAYERS = [
 BN_PER_KIND = {"relu": 1, "add": 1, "plain": 1, "pool": 1, "add_bn": 2}
 assert sum(n * BN_PER_KIND[k] for _, _, k, n in LAYERS) == 53
 
+# torch's bf16 add, as autograd launches it to sum two gradients (the fp32
+# adds that accumulate parameter gradients stay in "other")
+BF16_ADD = "CUDAFunctor_add<c10::BFloat16>"
 # kernel families: our kernels by their name without "_kernel", torch's pool
 # kernels by theirs; "other" is every other kernel the timed call launched
 FAMILIES = ["bn_fwd_reduce", "bn_fwd_finalize", "bn_fwd_apply",
             "bn_fwd_pool_apply", "bn_fwd_apply_add_bn",
             "max_pool_forward_nhwc",
-            "bn_bwd_reduce", "bn_bwd_finalize", "bn_bwd_apply",
-            "max_pool_backward_nhwc", "other"]
+            "bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_finalize",
+            "bn_bwd_apply", "max_pool_backward_nhwc", BF16_ADD, "other"]
 ROTATE_BYTES = 1 << 30
 
 
@@ -132,6 +144,40 @@ def expected_launches(kind, split):
         if kind == "pool":
             n["max_pool_forward_nhwc"] = n["max_pool_backward_nhwc"] = 1
     return n
+
+
+def join_bytes(kind, n_elem, C, gm_rows, pair):
+    """family_bytes for a tail whose dy arrives as two addends. pair: the
+    join reduce reads x and both addends and writes dz, the apply reads x and
+    dz; for add_bn the downsample branch then runs the mask-less backward on
+    dz. Otherwise torch's add (two reads, one write) comes first and backward
+    is the single-gradient one, which reads the mask in reduce and apply and,
+    for `add`, writes dres."""
+    e, mask, part = 2 * n_elem, n_elem // 8, 2 * gm_rows * C * 4
+    out = family_bytes(kind, n_elem, C, gm_rows, True)
+    two = 2 if kind == "add_bn" else 1
+    if not pair:
+        out[BF16_ADD] = 3 * e
+        return out
+    out["bn_bwd_reduce_join"] = 4 * e + mask + part
+    out["bn_bwd_reduce"] = (two - 1) * (2 * e + part)
+    out["bn_bwd_apply"] = two * 3 * e
+    return out
+
+
+def join_launches(kind, pair):
+    n = expected_launches(kind, False)
+    if pair:
+        n["bn_bwd_reduce_join"] = 1
+        n["bn_bwd_reduce"] -= 1
+    else:
+        n[BF16_ADD] = 1
+    return n
+
+
+# tails of ResNet-50 whose output has two consumers: all but layer4's last
+def join_count(C, kind, count):
+    return count - 1 if (C, kind) == (2048, "add") else count
 
 
 def reduce_gm(M, C):
@@ -212,6 +258,9 @@ def main():
              for k in ("pool", "add_bn")}
     ab_bytes = {k: {p: dict.fromkeys(FAMILIES, 0) for p in ("fused", "split")}
                 for k in ("pool", "add_bn")}
+    join_us = {p: dict.fromkeys(FAMILIES, 0.0) for p in ("fused", "split")}
+    join_bytes_sum = {p: dict.fromkeys(FAMILIES, 0)
+                      for p in ("fused", "split")}
     for (C, HW, kind, count) in LAYERS:
         n_elem = N * C * HW * HW
         sets = max(2, min(16, ROTATE_BYTES // (2 * n_elem)))
@@ -269,6 +318,34 @@ def main():
                     ab_bytes[kind][path][f] += count * nb[f]
         line = (f"{C:5d} {HW:4d} {kind:>5} {count:3d} "
                 + " ".join(f"{kt[f]:13.1f}" for f in FAMILIES))
+        join_lines = []
+        if args.ab and kind in ("add", "add_bn"):
+            g2 = [mk() for _ in range(sets)]
+
+            def join_fwd_bwd(pair):
+                i = turn[0] = (turn[0] + 1) % sets
+                xg = xs[i].detach().requires_grad_(True)
+                rg = rs[i].detach().requires_grad_(True)
+                if kind == "add_bn":
+                    y = bn.forward_add_bn(xg, rg, bn_d, pair=pair)
+                else:
+                    y = fused_bn_train(xg, w, b, rm, rv, relu=True,
+                                       residual=rg, ws=ws, pair=pair)
+                # one handle fed both gradients: autograd adds them first
+                torch.autograd.backward(y if pair else [y, y], [gs[i], g2[i]])
+
+            for path, pair in (("fused", True), ("split", False)):
+                t = kernel_times(lambda: join_fwd_bwd(pair), args.iters,
+                                 join_launches(kind, pair))
+                nb = join_bytes(kind, n_elem, C, gm, pair)
+                for f in FAMILIES:
+                    join_us[path][f] += join_count(C, kind, count) * t[f]
+                    join_bytes_sum[path][f] += \
+                        join_count(C, kind, count) * nb[f]
+                join_lines.append(
+                    f"{'':5} {'':4} {'join':>5} {path[:3]:>3} "
+                    + " ".join(f"{t[f]:13.1f}" for f in FAMILIES))
+            del g2
         if args.miopen:
             bn = torch.nn.BatchNorm2d(C).to(dev)
 
@@ -286,6 +363,8 @@ def main():
             line += (f" {time_fn(fused_fwd_bwd, args.iters) * 1e3:9.1f}"
                      f" {time_fn(miopen_fwd_bwd, args.iters) * 1e3:9.1f}")
         print(line, flush=True)
+        for jl in join_lines:
+            print(jl, flush=True)
         del xs, rs, gs
 
     print(f"# per training step (53 layers, batch {N}), bytes from shapes")
@@ -316,6 +395,27 @@ def main():
                for p in ("split", "fused")]
         print(f"{'sum':>24} {tot[0]:8.3f} {gbs[0]:7.2f} {'':>6} | "
               f"{tot[1]:8.3f} {gbs[1]:7.2f}")
+    print("# join: the 15 two-consumer block boundaries (11 add, 4 add_bn "
+          "tails), forward + backward per training step, autograd's add + "
+          "single-gradient backward | two-handle tails")
+    print(f"{'family':>24} {'ms':>8} {'GB':>7} {'TB/s':>6} | "
+          f"{'ms':>8} {'GB':>7} {'TB/s':>6}")
+    for f in FAMILIES:
+        cells = []
+        for path in ("split", "fused"):
+            ms = join_us[path][f] / 1e3
+            gb = join_bytes_sum[path][f] / 1e9
+            rate = f"{gb / ms:6.2f}" if ms and gb else f"{'-':>6}"
+            cells.append(f"{ms:8.3f} {gb:7.2f} {rate}")
+        print(f"{f:>24} " + " | ".join(cells))
+    tot = [sum(join_us[p].values()) / 1e3 for p in ("split", "fused")]
+    gbs = [sum(join_bytes_sum[p].values()) / 1e9 for p in ("split", "fused")]
+    print(f"{'sum':>24} {tot[0]:8.3f} {gbs[0]:7.2f} {'':>6} | "
+          f"{tot[1]:8.3f} {gbs[1]:7.2f}")
+    bwd = ("bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_apply",
+           BF16_ADD)
+    tb = [sum(join_us[p][f] for f in bwd) / 1e3 for p in ("split", "fused")]
+    print(f"{'backward streams only':>24} {tb[0]:8.3f} {'':>14} | {tb[1]:8.3f}")
 
 
 if __name__ == "__main__":

@@ -9,8 +9,9 @@ MARKER is a substring of a kernel that runs exactly once per training step
 window runs from the STEPS-th last launch of that kernel (default 10) to the
 last one, so it holds exactly STEPS steps of the replayed graph, after the
 warm-up and any MIOpen find. Prints calls per step and ms per step of every BN
-kernel instantiation and of the pool kernels, the BN-family totals, and the
-sum over all kernels.
+kernel instantiation, of the pool kernels and of torch's bf16 add (the
+gradient adds at the block inputs), the BN-family totals, and the sum over
+all kernels.
 """
 import csv
 import re
@@ -18,13 +19,17 @@ import sys
 
 FAMILIES = ["bn_fwd_reduce", "bn_fwd_finalize", "bn_fwd_apply",
             "bn_fwd_pool_apply", "bn_fwd_apply_add_bn", "bn_bwd_reduce",
-            "bn_bwd_finalize", "bn_bwd_apply", "max_pool_forward_nhwc",
-            "max_pool_backward_nhwc"]
+            "bn_bwd_reduce_join", "bn_bwd_finalize", "bn_bwd_apply",
+            "max_pool_forward_nhwc", "max_pool_backward_nhwc"]
+# listed beside the BN kernels, not counted among them
+ADD = "CUDAFunctor_add<c10::BFloat16>"
 
 
 def short(name):
     """Kernel name with its template arguments, without the parameter list."""
     m = re.search(r"(bn_\w+_kernel(<[^>]*>)?|max_pool_\w+_nhwc)", name)
+    if m is None and ADD in name:
+        return ADD
     return m.group(1) if m else None
 
 
@@ -50,6 +55,8 @@ def main():
         c = per.setdefault(k, [0, 0.0])
         c[0] += 1
         c[1] += d / 1e6
+        if k == ADD:
+            continue
         f = next(f for f in FAMILIES
                  if (f + "_kernel" if f.startswith("bn_") else f) in k)
         fam[f] += d / 1e6
