@@ -26,6 +26,20 @@
 // one after the other in their old order: the sums do not change by a bit.
 #define BN_RED_U 4
 #define BN_FIN_U 8
+// Rows in flight in the streaming apply kernels, per family: forward
+// (bn_fwd_apply_kernel, bn_fwd_apply_add_bn_kernel), backward
+// (bn_bwd_apply_kernel but its pool variant) and the two-branch backward
+// (bn_bwd_apply2_kernel). These kernels are elementwise: the value only
+// moves time. 1 leaves the one-row loop alone.
+#ifndef BN_APPLY_FWD_U
+#define BN_APPLY_FWD_U 2
+#endif
+#ifndef BN_APPLY_BWD_U
+#define BN_APPLY_BWD_U 2
+#endif
+#ifndef BN_APPLY2_U
+#define BN_APPLY2_U 2
+#endif
 // how the backward kernels get the ReLU mask: not at all, from the sign of
 // the stored y, or from the bit-packed mask the forward apply kernel wrote
 #define BN_RELU_NONE 0
@@ -109,6 +123,32 @@ __device__ __forceinline__ void unpack8(const Raw8<__hip_bfloat16>& r,
 __device__ __forceinline__ void unpack8(const Raw8<float>& r, float* v) {
   v[0] = r.a.x; v[1] = r.a.y; v[2] = r.a.z; v[3] = r.a.w;
   v[4] = r.b.x; v[5] = r.b.y; v[6] = r.b.z; v[7] = r.b.w;
+}
+// Loads through a const __restrict__ kernel argument are tied to nothing but
+// their address and their use, so instruction selection may sink them below
+// a sched_barrier to where they are consumed; in the backward apply kernels
+// and in some forward instantiations it does. An empty asm that takes the registers
+// of a row makes the row opaque at that point: its loads are issued (and
+// waited for) above it, every use stays below it.
+typedef unsigned bn_u32x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void pin8(Raw8<__hip_bfloat16>& r) {
+  bn_u32x4 v = {r.a.x, r.a.y, r.a.z, r.a.w};
+  asm volatile("" : "+v"(v));
+  r.a = make_uint4(v.x, v.y, v.z, v.w);
+}
+__device__ __forceinline__ void pin8(Raw8<float>& r) {
+  bn_u32x4 a = {__float_as_uint(r.a.x), __float_as_uint(r.a.y),
+                __float_as_uint(r.a.z), __float_as_uint(r.a.w)};
+  bn_u32x4 b = {__float_as_uint(r.b.x), __float_as_uint(r.b.y),
+                __float_as_uint(r.b.z), __float_as_uint(r.b.w)};
+  asm volatile("" : "+v"(a), "+v"(b));
+  r.a = make_float4(__uint_as_float(a.x), __uint_as_float(a.y),
+                    __uint_as_float(a.z), __uint_as_float(a.w));
+  r.b = make_float4(__uint_as_float(b.x), __uint_as_float(b.y),
+                    __uint_as_float(b.z), __uint_as_float(b.w));
+}
+__device__ __forceinline__ void pin8(unsigned& bits) {
+  asm volatile("" : "+v"(bits));
 }
 // dz = dy where the mask bit is set, else 0
 __device__ __forceinline__ void apply_mask8(unsigned bits, float* dv) {
@@ -337,14 +377,53 @@ __global__ void bn_fwd_finalize_kernel(const float* __restrict__ partial_sum,
 // MASK (with RELU): also write the ReLU mask of the stored y, one bit per
 // element: mask is [M, C/8] uint8 row-major, bit k of byte (m, c0/8) is set
 // iff y[m, c0+k] > 0. A thread owns 8 channels, so it writes one byte per row.
+//
+// The streaming apply kernels (this one, bn_fwd_apply_add_bn_kernel,
+// bn_bwd_apply_kernel, bn_bwd_apply2_kernel) share one loop shape: per trip a
+// thread issues the raw loads of every stream for U rows ahead of a
+// sched_barrier, then computes and stores the U rows; a one-row loop takes
+// what is left. With one row per trip the loop waited for its loads and, as
+// vmcnt counts stores too, for the previous row's store, with nothing in
+// flight while it computed. The host sizes the grid so that the rows of a
+// thread are a multiple of U wherever M allows (bn_apply_gm in ext.hip).
+// The arithmetic is spelled as the one-row loops compiled it (x*scale+shift
+// contracted to one fma), with contraction off, so that no unrolling moves a
+// bit: tests/test_bn_pool_gpu.py and tests/test_bn_add_bn_gpu.py compare this
+// kernel with the pool and joint-tail kernels, which spell fmaf as well.
 template <typename T, bool RELU, bool ADD, bool MASK>
-__global__ void bn_fwd_apply_kernel(const T* __restrict__ x,
-                                    const T* __restrict__ res,
-                                    T* __restrict__ y,
-                                    unsigned char* __restrict__ mask,
-                                    const float* __restrict__ scale,
-                                    const float* __restrict__ shift, long M,
-                                    int C) {
+__device__ __forceinline__ void bn_fwd_apply_row(
+    const Raw8<T>& rx, const Raw8<T>& rr, const float* sc, const float* sh,
+    T* __restrict__ y, unsigned char* __restrict__ mask, long m, int C,
+    int c0) {
+#pragma clang fp contract(off)
+  float v[BN_VEC];
+  unpack8(rx, v);
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) v[k] = fmaf(v[k], sc[k], sh[k]);
+  if (ADD) {
+    float r[BN_VEC];
+    unpack8(rr, r);
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) v[k] += r[k];
+  }
+  if (RELU) {
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) v[k] = fmaxf(v[k], 0.f);
+  }
+  if (MASK)
+    mask[m * (C / BN_VEC) + c0 / BN_VEC] =
+        (unsigned char)store8_mask(y + m * C + c0, v);
+  else
+    store8(y + m * C + c0, v);
+}
+
+template <typename T, bool RELU, bool ADD, bool MASK>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+bn_fwd_apply_kernel(const T* __restrict__ x, const T* __restrict__ res,
+                    T* __restrict__ y, unsigned char* __restrict__ mask,
+                    const float* __restrict__ scale,
+                    const float* __restrict__ shift, long M, int C) {
+  constexpr int U = BN_APPLY_FWD_U;
   int tx_count = min(C / BN_VEC, (int)blockDim.x);
   int tx = threadIdx.x % tx_count;
   int ty = threadIdx.x / tx_count;
@@ -354,27 +433,37 @@ __global__ void bn_fwd_apply_kernel(const T* __restrict__ x,
   float sc[BN_VEC], sh[BN_VEC];
   load8(scale + c0, sc);
   load8(shift + c0, sh);
-  for (long m = (long)blockIdx.x * rows_per_blk + ty; m < M;
-       m += (long)gridDim.x * rows_per_blk) {
-    float v[BN_VEC];
-    load8(x + m * C + c0, v);
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  if (U > 1) {
+    for (; m + (U - 1) * stride < M; m += U * stride) {
+      Raw8<T> rx[U], rr[U];
 #pragma unroll
-    for (int k = 0; k < BN_VEC; ++k) v[k] = v[k] * sc[k] + sh[k];
-    if (ADD) {
-      float r[BN_VEC];
-      load8(res + m * C + c0, r);
+      for (int u = 0; u < U; ++u) {
+        rx[u] = load8raw(x + (m + u * stride) * C + c0);
+        if (ADD) rr[u] = load8raw(res + (m + u * stride) * C + c0);
+      }
+      // every load of the trip is issued before the first row is consumed
 #pragma unroll
-      for (int k = 0; k < BN_VEC; ++k) v[k] += r[k];
+      for (int u = 0; u < U; ++u) {
+        pin8(rx[u]);
+        if (ADD) pin8(rr[u]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bn_fwd_apply_row<T, RELU, ADD, MASK>(rx[u], rr[u], sc, sh, y, mask,
+                                             m + u * stride, C, c0);
+        // one row unpacked at a time: interleaved, the U rows' fp32 values
+        // cost more registers than the rows still packed
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
-    if (RELU) {
-#pragma unroll
-      for (int k = 0; k < BN_VEC; ++k) v[k] = fmaxf(v[k], 0.f);
-    }
-    if (MASK)
-      mask[m * (C / BN_VEC) + c0 / BN_VEC] =
-          (unsigned char)store8_mask(y + m * C + c0, v);
-    else
-      store8(y + m * C + c0, v);
+  }
+  for (; m < M; m += stride) {
+    Raw8<T> rx = load8raw(x + m * C + c0), rr;
+    if (ADD) rr = load8raw(res + m * C + c0);
+    bn_fwd_apply_row<T, RELU, ADD, MASK>(rx, rr, sc, sh, y, mask, m, C, c0);
   }
 }
 
@@ -458,11 +547,32 @@ __global__ void bn_fwd_pool_apply_kernel(const T* __restrict__ x,
 // rounded to T first: it is the identity tensor that the plain apply kernel
 // would have stored and the ADD variant read back.
 template <typename T>
-__global__ void bn_fwd_apply_add_bn_kernel(
+__device__ __forceinline__ void bn_fwd_apply_add_bn_row(
+    const Raw8<T>& rz, const Raw8<T>& rzd, const float* sc, const float* sh,
+    const float* scd, const float* shd, T* __restrict__ y,
+    unsigned char* __restrict__ mask, long m, int C, int c0) {
+#pragma clang fp contract(off)
+  float v[BN_VEC], r[BN_VEC];
+  unpack8(rz, v);
+  unpack8(rzd, r);
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) {
+    v[k] = fmaf(v[k], sc[k], sh[k]);
+    v[k] += round_to(fmaf(r[k], scd[k], shd[k]), (const T*)nullptr);
+    v[k] = fmaxf(v[k], 0.f);
+  }
+  mask[m * (C / BN_VEC) + c0 / BN_VEC] =
+      (unsigned char)store8_mask(y + m * C + c0, v);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+bn_fwd_apply_add_bn_kernel(
     const T* __restrict__ z, const T* __restrict__ zd, T* __restrict__ y,
     unsigned char* __restrict__ mask, const float* __restrict__ scale,
     const float* __restrict__ shift, const float* __restrict__ scale_d,
     const float* __restrict__ shift_d, long M, int C) {
+  constexpr int U = BN_APPLY_FWD_U;
   int tx_count = min(C / BN_VEC, (int)blockDim.x);
   int tx = threadIdx.x % tx_count;
   int ty = threadIdx.x / tx_count;
@@ -474,20 +584,35 @@ __global__ void bn_fwd_apply_add_bn_kernel(
   load8(shift + c0, sh);
   load8(scale_d + c0, scd);
   load8(shift_d + c0, shd);
-  for (long m = (long)blockIdx.x * rows_per_blk + ty; m < M;
-       m += (long)gridDim.x * rows_per_blk) {
-    float v[BN_VEC], r[BN_VEC];
-    load8(z + m * C + c0, v);
-    load8(zd + m * C + c0, r);
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  if (U > 1) {
+    for (; m + (U - 1) * stride < M; m += U * stride) {
+      Raw8<T> rz[U], rzd[U];
 #pragma unroll
-    for (int k = 0; k < BN_VEC; ++k) {
-      v[k] = fmaf(v[k], sc[k], sh[k]);
-      v[k] += round_to(fmaf(r[k], scd[k], shd[k]), (const T*)nullptr);
-      v[k] = fmaxf(v[k], 0.f);
+      for (int u = 0; u < U; ++u) {
+        rz[u] = load8raw(z + (m + u * stride) * C + c0);
+        rzd[u] = load8raw(zd + (m + u * stride) * C + c0);
+      }
+      // every load of the trip is issued before the first row is consumed
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        pin8(rz[u]);
+        pin8(rzd[u]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        bn_fwd_apply_add_bn_row<T>(rz[u], rzd[u], sc, sh, scd, shd, y, mask,
+                                   m + u * stride, C, c0);
+        __builtin_amdgcn_sched_barrier(0);  // see bn_fwd_apply_kernel
+      }
     }
-    mask[m * (C / BN_VEC) + c0 / BN_VEC] =
-        (unsigned char)store8_mask(y + m * C + c0, v);
   }
+  for (; m < M; m += stride)
+    bn_fwd_apply_add_bn_row<T>(load8raw(z + m * C + c0),
+                               load8raw(zd + m * C + c0), sc, sh, scd, shd, y,
+                               mask, m, C, c0);
 }
 
 // ------------------------------------------------------------- bwd reduce
@@ -724,6 +849,119 @@ bn_bwd_reduce_join_kernel(const T* __restrict__ x, const T* __restrict__ dy_a,
   }
 }
 
+// ------------------------------- bwd reduce, two gradients and two branches
+// The tail relu(bn3(z) + bn_ds(zd)) of a block with a downsample: both BNs
+// get the same dz, so one pass forms it (as bn_bwd_reduce_join_kernel does),
+// stores it, and takes sum dz once and sum dz*xhat of each branch. Grid, rows
+// per thread, order and expressions are those of bn_bwd_reduce_join_kernel on
+// z and of bn_bwd_reduce_kernel<T, BN_RELU_NONE> on (zd, dz), so each of the
+// three partial matrices is what those kernels write, bit for bit.
+// BN_JOIN2_U rows in flight: 4 streams of 16 B and the mask byte per row.
+#ifndef BN_JOIN2_U
+#define BN_JOIN2_U 2
+#endif
+template <typename T>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+__attribute__((amdgpu_waves_per_eu(1)))
+bn_bwd_reduce_join2_kernel(const T* __restrict__ z, const T* __restrict__ zd,
+                           const T* __restrict__ dy_a,
+                           const T* __restrict__ dy_b,
+                           const unsigned char* __restrict__ mask,
+                           const float* __restrict__ save_mean,
+                           const float* __restrict__ save_rstd,
+                           const float* __restrict__ save_mean_d,
+                           const float* __restrict__ save_rstd_d,
+                           float* __restrict__ partial_dz,
+                           float* __restrict__ partial_dzxh,
+                           float* __restrict__ partial_dzxh_d,
+                           T* __restrict__ dz, long M, int C) {
+#pragma clang fp contract(off)  // see bn_fwd_reduce_kernel
+  int tx_count = min(C / BN_VEC, (int)blockDim.x);
+  int tx = threadIdx.x % tx_count;
+  int ty = threadIdx.x / tx_count;
+  int rows_per_blk = blockDim.x / tx_count;
+  int c0 = (blockIdx.y * tx_count + tx) * BN_VEC;
+  if (c0 >= C) return;
+  float mean[BN_VEC], rstd[BN_VEC], mean_d[BN_VEC], rstd_d[BN_VEC];
+  load8(save_mean + c0, mean);
+  load8(save_rstd + c0, rstd);
+  load8(save_mean_d + c0, mean_d);
+  load8(save_rstd_d + c0, rstd_d);
+  float s[BN_VEC] = {0}, t[BN_VEC] = {0}, td[BN_VEC] = {0};
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  for (; m + (BN_JOIN2_U - 1) * stride < M; m += BN_JOIN2_U * stride) {
+    Raw8<T> rz[BN_JOIN2_U], rzd[BN_JOIN2_U], ra[BN_JOIN2_U], rb[BN_JOIN2_U];
+    unsigned rm[BN_JOIN2_U];
+#pragma unroll
+    for (int u = 0; u < BN_JOIN2_U; ++u) {
+      const long mu = m + u * stride;
+      rz[u] = load8raw(z + mu * C + c0);
+      rzd[u] = load8raw(zd + mu * C + c0);
+      ra[u] = load8raw(dy_a + mu * C + c0);
+      rb[u] = load8raw(dy_b + mu * C + c0);
+      rm[u] = mask[mu * (C / BN_VEC) + c0 / BN_VEC];
+    }
+    // every load of the trip is issued before the first row is consumed
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < BN_JOIN2_U; ++u) {
+      float zv[BN_VEC], zdv[BN_VEC], av[BN_VEC], bv[BN_VEC], dv[BN_VEC];
+      unpack8(rz[u], zv);
+      unpack8(rzd[u], zdv);
+      unpack8(ra[u], av);
+      unpack8(rb[u], bv);
+      bn_join_dz8<T>(av, bv, rm[u], dv);
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) {
+        s[k] += dv[k];
+        t[k] = fmaf(dv[k] * (zv[k] - mean[k]), rstd[k], t[k]);
+        td[k] = fmaf(dv[k] * (zdv[k] - mean_d[k]), rstd_d[k], td[k]);
+      }
+      store8(dz + (m + u * stride) * C + c0, dv);
+    }
+  }
+  for (; m < M; m += stride) {
+    float zv[BN_VEC], zdv[BN_VEC], av[BN_VEC], bv[BN_VEC], dv[BN_VEC];
+    load8(z + m * C + c0, zv);
+    load8(zd + m * C + c0, zdv);
+    load8(dy_a + m * C + c0, av);
+    load8(dy_b + m * C + c0, bv);
+    bn_join_dz8<T>(av, bv, mask[m * (C / BN_VEC) + c0 / BN_VEC], dv);
+#pragma unroll
+    for (int k = 0; k < BN_VEC; ++k) {
+      s[k] += dv[k];
+      t[k] = fmaf(dv[k] * (zv[k] - mean[k]), rstd[k], t[k]);
+      td[k] = fmaf(dv[k] * (zdv[k] - mean_d[k]), rstd_d[k], td[k]);
+    }
+    store8(dz + m * C + c0, dv);
+  }
+  __shared__ float ls[BLOCK_THREADS * BN_VEC];
+  __shared__ float lt[BLOCK_THREADS * BN_VEC];
+  __shared__ float ltd[BLOCK_THREADS * BN_VEC];
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) {
+    ls[threadIdx.x * BN_VEC + k] = s[k];
+    lt[threadIdx.x * BN_VEC + k] = t[k];
+    ltd[threadIdx.x * BN_VEC + k] = td[k];
+  }
+  __syncthreads();
+  if (ty == 0) {
+    for (int r = 1; r < rows_per_blk; ++r) {
+      int o = (r * tx_count + tx) * BN_VEC;
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) {
+        s[k] += ls[o + k];
+        t[k] += lt[o + k];
+        td[k] += ltd[o + k];
+      }
+    }
+    store8(partial_dz + (long)blockIdx.x * C + c0, s);
+    store8(partial_dzxh + (long)blockIdx.x * C + c0, t);
+    store8(partial_dzxh_d + (long)blockIdx.x * C + c0, td);
+  }
+}
+
 // ------------------------------------------------------------ bwd finalize
 // k1 = w*rstd ; k2 = sum_dz/M ; k3 = sum_dzxh/M ; dweight = sum_dzxh ;
 // dbias = sum_dz
@@ -763,8 +1001,27 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ partial_dz,
 
 // -------------------------------------------------------------- bwd apply
 // dx = k1*(dz - k2 - xhat*k3); dres = dz (if ADD)
+// Spelled as the one-row loop compiled it, contraction off (see
+// bn_fwd_apply_kernel): dz - k2 - xhat*k3 had become one fma on -xhat.
+__device__ __forceinline__ void bn_bwd_dx8(const float* xv, const float* dv,
+                                           const float* mean,
+                                           const float* rstd, const float* a1,
+                                           const float* a2, const float* a3,
+                                           float* o) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int k = 0; k < BN_VEC; ++k) {
+    float xhat = (xv[k] - mean[k]) * rstd[k];
+    o[k] = a1[k] * fmaf(-xhat, a3[k], dv[k] - a2[k]);
+  }
+}
+
+// The pool variant keeps its one-row loop: its nine gathered loads per row
+// are in flight already.
 template <typename T, int RELU, bool ADD>
-__global__ void bn_bwd_apply_kernel(const T* __restrict__ x,
+__global__ void
+__launch_bounds__(RELU == BN_RELU_POOL ? 1024 : BLOCK_THREADS)
+bn_bwd_apply_kernel(const T* __restrict__ x,
                                     const T* __restrict__ dy,
                                     const T* __restrict__ y,
                                     const unsigned char* __restrict__ mask,
@@ -787,18 +1044,157 @@ __global__ void bn_bwd_apply_kernel(const T* __restrict__ x,
   load8(k1 + c0, a1);
   load8(k2 + c0, a2);
   load8(k3 + c0, a3);
-  for (long m = (long)blockIdx.x * rows_per_blk + ty; m < M;
-       m += (long)gridDim.x * rows_per_blk) {
-    float xv[BN_VEC], dv[BN_VEC];
+  if (RELU == BN_RELU_POOL) {
+    for (long m = (long)blockIdx.x * rows_per_blk + ty; m < M;
+         m += (long)gridDim.x * rows_per_blk) {
+      float xv[BN_VEC], dv[BN_VEC];
+      load8(x + m * C + c0, xv);
+      bn_load_dz<T, RELU>(dy, y, mask, pool, m, C, c0, dv);
+      if (ADD) store8(dres + m * C + c0, dv);
+      float o[BN_VEC];
+#pragma unroll
+      for (int k = 0; k < BN_VEC; ++k) {
+        float xhat = (xv[k] - mean[k]) * rstd[k];
+        o[k] = a1[k] * (dv[k] - a2[k] - xhat * a3[k]);
+      }
+      store8(dx + m * C + c0, o);
+    }
+    return;
+  }
+  constexpr int U = BN_APPLY_BWD_U;
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  if (U > 1) {
+    for (; m + (U - 1) * stride < M; m += U * stride) {
+      Raw8<T> rx[U], rd[U], ry[U];
+      unsigned rm[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long mu = m + u * stride;
+        rx[u] = load8raw(x + mu * C + c0);
+        rd[u] = load8raw(dy + mu * C + c0);
+        if (RELU == BN_RELU_Y) ry[u] = load8raw(y + mu * C + c0);
+        if (RELU == BN_RELU_MASK)
+          rm[u] = mask[mu * (C / BN_VEC) + c0 / BN_VEC];
+      }
+      // every load of the trip is issued before the first row is consumed
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        pin8(rx[u]);
+        pin8(rd[u]);
+        if (RELU == BN_RELU_Y) pin8(ry[u]);
+        if (RELU == BN_RELU_MASK) pin8(rm[u]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long mu = m + u * stride;
+        float xv[BN_VEC], dv[BN_VEC], o[BN_VEC];
+        unpack8(rx[u], xv);
+        unpack8(rd[u], dv);
+        if (RELU == BN_RELU_Y) {
+          float yv[BN_VEC];
+          unpack8(ry[u], yv);
+#pragma unroll
+          for (int k = 0; k < BN_VEC; ++k) dv[k] = yv[k] > 0.f ? dv[k] : 0.f;
+        }
+        if (RELU == BN_RELU_MASK) apply_mask8(rm[u], dv);
+        if (ADD) store8(dres + mu * C + c0, dv);
+        bn_bwd_dx8(xv, dv, mean, rstd, a1, a2, a3, o);
+        store8(dx + mu * C + c0, o);
+        __builtin_amdgcn_sched_barrier(0);  // see bn_fwd_apply_kernel
+      }
+    }
+  }
+  for (; m < M; m += stride) {
+    float xv[BN_VEC], dv[BN_VEC], o[BN_VEC];
     load8(x + m * C + c0, xv);
     bn_load_dz<T, RELU>(dy, y, mask, pool, m, C, c0, dv);
     if (ADD) store8(dres + m * C + c0, dv);
-    float o[BN_VEC];
-#pragma unroll
-    for (int k = 0; k < BN_VEC; ++k) {
-      float xhat = (xv[k] - mean[k]) * rstd[k];
-      o[k] = a1[k] * (dv[k] - a2[k] - xhat * a3[k]);
-    }
+    bn_bwd_dx8(xv, dv, mean, rstd, a1, a2, a3, o);
     store8(dx + m * C + c0, o);
+  }
+}
+
+// ------------------------------------------------- bwd apply, two branches
+// The apply of the relu(bn3(z) + bn_ds(zd)) tail: one read of dz (already
+// masked, written by bn_bwd_reduce_join2_kernel) gives dx of both branches,
+// each with the arithmetic of bn_bwd_apply_kernel<T, BN_RELU_NONE, false>.
+// k2 = sum dz / M is one value for both branches.
+template <typename T>
+__global__ void __launch_bounds__(BLOCK_THREADS)
+bn_bwd_apply2_kernel(const T* __restrict__ z, const T* __restrict__ zd,
+                     const T* __restrict__ dz,
+                     const float* __restrict__ save_mean,
+                     const float* __restrict__ save_rstd,
+                     const float* __restrict__ save_mean_d,
+                     const float* __restrict__ save_rstd_d,
+                     const float* __restrict__ k1, const float* __restrict__ k2,
+                     const float* __restrict__ k3,
+                     const float* __restrict__ k1_d,
+                     const float* __restrict__ k3_d, T* __restrict__ dx,
+                     T* __restrict__ dx_d, long M, int C) {
+  constexpr int U = BN_APPLY2_U;
+  int tx_count = min(C / BN_VEC, (int)blockDim.x);
+  int tx = threadIdx.x % tx_count;
+  int ty = threadIdx.x / tx_count;
+  int rows_per_blk = blockDim.x / tx_count;
+  int c0 = (blockIdx.y * tx_count + tx) * BN_VEC;
+  if (c0 >= C) return;
+  float mean[BN_VEC], rstd[BN_VEC], a1[BN_VEC], a2[BN_VEC], a3[BN_VEC];
+  float mean_d[BN_VEC], rstd_d[BN_VEC], a1_d[BN_VEC], a3_d[BN_VEC];
+  load8(save_mean + c0, mean);
+  load8(save_rstd + c0, rstd);
+  load8(k1 + c0, a1);
+  load8(k2 + c0, a2);
+  load8(k3 + c0, a3);
+  load8(save_mean_d + c0, mean_d);
+  load8(save_rstd_d + c0, rstd_d);
+  load8(k1_d + c0, a1_d);
+  load8(k3_d + c0, a3_d);
+  const long stride = (long)gridDim.x * rows_per_blk;
+  long m = (long)blockIdx.x * rows_per_blk + ty;
+  if (U > 1) {
+    for (; m + (U - 1) * stride < M; m += U * stride) {
+      Raw8<T> rz[U], rzd[U], rd[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long mu = m + u * stride;
+        rz[u] = load8raw(z + mu * C + c0);
+        rzd[u] = load8raw(zd + mu * C + c0);
+        rd[u] = load8raw(dz + mu * C + c0);
+      }
+      // every load of the trip is issued before the first row is consumed
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        pin8(rz[u]);
+        pin8(rzd[u]);
+        pin8(rd[u]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const long mu = m + u * stride;
+        float zv[BN_VEC], zdv[BN_VEC], dv[BN_VEC], o[BN_VEC];
+        unpack8(rz[u], zv);
+        unpack8(rzd[u], zdv);
+        unpack8(rd[u], dv);
+        bn_bwd_dx8(zv, dv, mean, rstd, a1, a2, a3, o);
+        store8(dx + mu * C + c0, o);
+        bn_bwd_dx8(zdv, dv, mean_d, rstd_d, a1_d, a2, a3_d, o);
+        store8(dx_d + mu * C + c0, o);
+        __builtin_amdgcn_sched_barrier(0);  // see bn_fwd_apply_kernel
+      }
+    }
+  }
+  for (; m < M; m += stride) {
+    float zv[BN_VEC], zdv[BN_VEC], dv[BN_VEC], o[BN_VEC];
+    load8(z + m * C + c0, zv);
+    load8(zd + m * C + c0, zdv);
+    load8(dz + m * C + c0, dv);
+    bn_bwd_dx8(zv, dv, mean, rstd, a1, a2, a3, o);
+    store8(dx + m * C + c0, o);
+    bn_bwd_dx8(zdv, dv, mean_d, rstd_d, a1_d, a2, a3_d, o);
+    store8(dx_d + m * C + c0, o);
   }
 }

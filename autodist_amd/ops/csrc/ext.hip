@@ -47,6 +47,20 @@ inline int bn_grid_m(const BNGeom& g, long target_blocks) {
   return (int)std::min(gm, cap);
 }
 
+// Grid of a streaming apply kernel that holds U rows in flight: at most the
+// 4096 / grid_c blocks of bn_grid_m, and as many as give every thread a whole
+// number of U-row trips (the last blocks fall short where the rows do not
+// divide). 2048 x 7 x 7 at batch 512 has 25088 block-rows: 3136 blocks of two
+// 4-row trips, where 4096 blocks would run one such trip and two or three
+// single rows. Fewer block-rows than U: one block, single rows.
+inline int bn_apply_gm(const BNGeom& g, int U) {
+  if (U == 1) return bn_grid_m(g, 4096);
+  long rows = (g.M + g.rows_per_blk - 1) / g.rows_per_blk;
+  long cap = std::max<long>(4096 / std::max(g.grid_c, 1), 1);
+  long trips = std::max<long>((rows + U * cap - 1) / (U * cap), 1);
+  return (int)((rows + U * trips - 1) / (U * trips));
+}
+
 // max partial rows for the two-stage BN reductions (2 blocks per CU).
 // NOTE: raising this to 2048 (8 blocks/CU) was MEASURED SLOWER on every
 // ResNet shape (tools/bn_microbench.py, 2026-09-14): the reduce stage is
@@ -164,7 +178,7 @@ std::vector<torch::Tensor> bn_fwd_impl(
                         x.options().dtype(torch::kUInt8));
   unsigned char* mp = with_mask ? mask.data_ptr<unsigned char>() : nullptr;
   auto y = torch::empty_like(x);
-  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  dim3 grid_a(bn_apply_gm(g, BN_APPLY_FWD_U), g.grid_c);
   auto st = cur_stream();
   const torch::Tensor* rp = res.has_value() ? &*res : nullptr;
 #define BN_FWD_APPLY(RELU, ADD, MASK)                                        \
@@ -302,7 +316,7 @@ std::vector<torch::Tensor> bn_fwd_add_bn_impl(
   auto y = torch::empty_like(z);
   auto mask = torch::empty({g.M, (long)(g.C / BN_VEC)},
                            z.options().dtype(torch::kUInt8));
-  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  dim3 grid_a(bn_apply_gm(g, BN_APPLY_FWD_U), g.grid_c);
   hipLaunchKernelGGL((bn_fwd_apply_add_bn_kernel<T>), grid_a,
                      dim3(BLOCK_THREADS), 0, cur_stream(), bn_ptr<const T>(z),
                      bn_ptr<const T>(zd), bn_ptr<T>(y),
@@ -372,7 +386,7 @@ std::vector<torch::Tensor> bn_bwd_impl(
   dim3 block(BLOCK_THREADS);
   int gm = bn_reduce_gm(g);
   dim3 grid_r(gm, g.grid_c);
-  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  dim3 grid_a(bn_apply_gm(g, BN_APPLY_BWD_U), g.grid_c);
   auto st = cur_stream();
   const float* sm = save_mean.data_ptr<float>();
   const float* sr = save_rstd.data_ptr<float>();
@@ -483,7 +497,7 @@ std::vector<torch::Tensor> bn_bwd_mask_join_impl(
   dim3 block(BLOCK_THREADS);
   int gm = bn_reduce_gm(g);
   dim3 grid_r(gm, g.grid_c);
-  dim3 grid_a(bn_grid_m(g, 4096), g.grid_c);
+  dim3 grid_a(bn_apply_gm(g, BN_APPLY_BWD_U), g.grid_c);
   auto st = cur_stream();
   const float* sm = save_mean.data_ptr<float>();
   const float* sr = save_rstd.data_ptr<float>();
@@ -517,6 +531,120 @@ std::vector<torch::Tensor> bn_bwd_mask_join(
   TORCH_CHECK(x.scalar_type() == torch::kFloat32);
   return bn_bwd_mask_join_impl<float>(x, dy_a, dy_b, mask, save_mean,
                                       save_rstd, weight, ws);
+}
+
+// Backward of relu(bn(z) + bn_d(zd)) for a dy that arrives as two addends:
+// bn_bwd_mask_join on z followed by the mask-less bn_bwd on (zd, dz), with
+// the two reduces and the two applies each done in one pass (10 tensor passes
+// where those run 12). Every output is what that pair of calls returns.
+// -> (dx, dweight, dbias, dz, dx_d, dweight_d, dbias_d)
+template <typename T>
+std::vector<torch::Tensor> bn_bwd_mask_join_bn_impl(
+    const torch::Tensor& z, const torch::Tensor& dy_a,
+    const torch::Tensor& dy_b, const torch::Tensor& mask,
+    const torch::Tensor& save_mean, const torch::Tensor& save_rstd,
+    const torch::Tensor& weight, const c10::optional<torch::Tensor>& ws,
+    const torch::Tensor& zd, const torch::Tensor& save_mean_d,
+    const torch::Tensor& save_rstd_d, const torch::Tensor& weight_d,
+    const c10::optional<torch::Tensor>& ws_d) {
+  auto g = bn_geom(z);
+  auto gd = bn_geom(zd);
+  TORCH_CHECK(gd.M == g.M && gd.C == g.C &&
+                  zd.scalar_type() == z.scalar_type() &&
+                  zd.device() == z.device(),
+              "bn_bwd_mask_join: z and zd must agree in shape and dtype");
+  for (const torch::Tensor* d : {&dy_a, &dy_b})
+    TORCH_CHECK(d->sizes() == z.sizes() &&
+                    d->scalar_type() == z.scalar_type() &&
+                    d->device() == z.device() &&
+                    d->is_contiguous(at::MemoryFormat::ChannelsLast),
+                "bn_bwd_mask_join: dy_a and dy_b must match x in shape, "
+                "dtype, device and channels_last layout");
+  TORCH_CHECK(!(ws.has_value() && ws_d.has_value()) ||
+                  ws->data_ptr() != ws_d->data_ptr(),
+              "bn_bwd_mask_join: the two BNs need workspaces of their own");
+  // ws rows as in bn_bwd_impl, one workspace per branch; the d branch's
+  // partial_dz rows stay unused: sum dz is taken once, into ws
+  auto fopt = weight.options().dtype(torch::kFloat32);
+  torch::Tensor w5 = ws.has_value() ? *ws
+      : torch::empty({2 * BN_GM_MAX + 3, (long)g.C}, fopt);
+  torch::Tensor w5d = ws_d.has_value() ? *ws_d
+      : torch::empty({2 * BN_GM_MAX + 3, (long)g.C}, fopt);
+  for (const torch::Tensor* w : {&w5, &w5d})
+    TORCH_CHECK(w->size(0) >= 2 * BN_GM_MAX + 3 && w->size(1) == g.C &&
+                w->is_contiguous());
+  TORCH_CHECK(mask.scalar_type() == torch::kUInt8 && mask.is_contiguous() &&
+                  mask.dim() == 2 && mask.size(0) == g.M &&
+                  mask.size(1) == g.C / BN_VEC && mask.device() == z.device(),
+              "mask must be the [M, C/8] uint8 tensor of bn_fwd_train_mask");
+  const unsigned char* mp = mask.data_ptr<unsigned char>();
+  float* wp = w5.data_ptr<float>();
+  float* wpd = w5d.data_ptr<float>();
+  float* partial_dz = wp;
+  float* partial_dzxh = wp + (long)BN_GM_MAX * g.C;
+  float* partial_dzxh_d = wpd + (long)BN_GM_MAX * g.C;
+  float* k1 = wp + (long)(2 * BN_GM_MAX + 0) * g.C;
+  float* k2 = wp + (long)(2 * BN_GM_MAX + 1) * g.C;
+  float* k3 = wp + (long)(2 * BN_GM_MAX + 2) * g.C;
+  float* k1_d = wpd + (long)(2 * BN_GM_MAX + 0) * g.C;
+  float* k2_d = wpd + (long)(2 * BN_GM_MAX + 1) * g.C;
+  float* k3_d = wpd + (long)(2 * BN_GM_MAX + 2) * g.C;
+  auto dweight = torch::empty({g.C}, fopt);
+  auto dbias = torch::empty({g.C}, fopt);
+  auto dweight_d = torch::empty({g.C}, fopt);
+  auto dbias_d = torch::empty({g.C}, fopt);
+  auto dx = torch::empty_like(z);
+  auto dx_d = torch::empty_like(zd);
+  auto dz = torch::empty_like(z);
+  dim3 block(BLOCK_THREADS);
+  int gm = bn_reduce_gm(g);
+  dim3 grid_r(gm, g.grid_c);
+  dim3 grid_a(bn_apply_gm(g, BN_APPLY2_U), g.grid_c);
+  dim3 grid_f((g.C + FIN_CH - 1) / FIN_CH), block_f(FIN_CH * FIN_LANES);
+  auto st = cur_stream();
+  const float* sm = save_mean.data_ptr<float>();
+  const float* sr = save_rstd.data_ptr<float>();
+  const float* smd = save_mean_d.data_ptr<float>();
+  const float* srd = save_rstd_d.data_ptr<float>();
+
+  hipLaunchKernelGGL((bn_bwd_reduce_join2_kernel<T>), grid_r, block, 0, st,
+                     bn_ptr<const T>(z), bn_ptr<const T>(zd),
+                     bn_ptr<const T>(dy_a), bn_ptr<const T>(dy_b), mp, sm, sr,
+                     smd, srd, partial_dz, partial_dzxh, partial_dzxh_d,
+                     bn_ptr<T>(dz), g.M, g.C);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, grid_f, block_f, 0, st,
+                     partial_dz, partial_dzxh, gm, weight.data_ptr<float>(),
+                     sr, k1, k2, k3, dweight.data_ptr<float>(),
+                     dbias.data_ptr<float>(), g.M, g.C);
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, grid_f, block_f, 0, st,
+                     partial_dz, partial_dzxh_d, gm,
+                     weight_d.data_ptr<float>(), srd, k1_d, k2_d, k3_d,
+                     dweight_d.data_ptr<float>(), dbias_d.data_ptr<float>(),
+                     g.M, g.C);
+  hipLaunchKernelGGL((bn_bwd_apply2_kernel<T>), grid_a, block, 0, st,
+                     bn_ptr<const T>(z), bn_ptr<const T>(zd),
+                     bn_ptr<const T>(dz), sm, sr, smd, srd, k1, k2, k3, k1_d,
+                     k3_d, bn_ptr<T>(dx), bn_ptr<T>(dx_d), g.M, g.C);
+  return {dx, dweight, dbias, dz, dx_d, dweight_d, dbias_d};
+}
+
+// Bound as a second signature of bn_bwd_mask_join: the arguments of the
+// one-BN call, then the downsample branch's zd, statistics, weight and ws.
+std::vector<torch::Tensor> bn_bwd_mask_join_bn(
+    torch::Tensor z, torch::Tensor dy_a, torch::Tensor dy_b,
+    torch::Tensor mask, torch::Tensor save_mean, torch::Tensor save_rstd,
+    torch::Tensor weight, c10::optional<torch::Tensor> ws, torch::Tensor zd,
+    torch::Tensor save_mean_d, torch::Tensor save_rstd_d,
+    torch::Tensor weight_d, c10::optional<torch::Tensor> ws_d) {
+  if (z.scalar_type() == torch::kBFloat16)
+    return bn_bwd_mask_join_bn_impl<__hip_bfloat16>(
+        z, dy_a, dy_b, mask, save_mean, save_rstd, weight, ws, zd,
+        save_mean_d, save_rstd_d, weight_d, ws_d);
+  TORCH_CHECK(z.scalar_type() == torch::kFloat32);
+  return bn_bwd_mask_join_bn_impl<float>(z, dy_a, dy_b, mask, save_mean,
+                                         save_rstd, weight, ws, zd,
+                                         save_mean_d, save_rstd_d, weight_d,
+                                         ws_d);
 }
 
 // bn_bwd for bn_fwd_train_pool: dy is the pooled dy, argmax the forward's
@@ -1309,6 +1437,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "bn_bwd_mask for dy = dy_a + dy_b, the add done in the reduce: (x, "
         "dy_a, dy_b, mask, save_mean, save_rstd, weight, ws) -> (dx, "
         "dweight, dbias, dz); dz is the masked sum, the split path's dres");
+  m.def("bn_bwd_mask_join", &bn_bwd_mask_join_bn,
+        "the same for the tail relu(bn(z) + bn_d(zd)), both branches in one "
+        "reduce and one apply: (z, dy_a, dy_b, mask, save_mean, save_rstd, "
+        "weight, ws, zd, save_mean_d, save_rstd_d, weight_d, ws_d) -> (dx, "
+        "dweight, dbias, dz, dx_d, dweight_d, dbias_d), what the one-BN call "
+        "on z and bn_bwd(zd, dz) return");
   m.def("bn_fwd_train_pool", &bn_fwd_train_pool,
         "bn + relu + 3x3/stride 2/pad 1 max-pool: (x, weight, bias, "
         "running_mean, running_var, eps, momentum, ws) -> (pooled y, "
@@ -1324,6 +1458,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("BN_RED_U") = BN_RED_U;
   m.attr("BN_FIN_U") = BN_FIN_U;
   m.attr("BN_JOIN_U") = BN_JOIN_U;
+  m.attr("BN_JOIN2_U") = BN_JOIN2_U;
+  // and in the streaming apply kernels (tests mirror bn_apply_gm with them)
+  m.attr("BN_APPLY_FWD_U") = BN_APPLY_FWD_U;
+  m.attr("BN_APPLY_BWD_U") = BN_APPLY_BWD_U;
+  m.attr("BN_APPLY2_U") = BN_APPLY2_U;
   m.def("psgd_mq", &psgd_mq, "PowerSGD P = M @ Q (MFMA f32 16x16x4)");
   m.def("psgd_mtp", &psgd_mtp, "PowerSGD Qn = M^T @ P (MFMA f32 16x16x4)");
   m.def("psgd_decompress_ef", &psgd_decompress_ef,

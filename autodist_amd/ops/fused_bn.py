@@ -149,8 +149,9 @@ class _FusedBNPoolFunction(torch.autograd.Function):
 class _FusedBNAddBNFunction(torch.autograd.Function):
     """relu(bn(z) + bn_d(zd)) with one apply kernel; backward is bn_bwd_mask
     on each branch, both with the dy and the packed mask of y. With `pair`
-    and both handles used, bn_bwd_mask_join on z adds the two gradients and
-    leaves the masked sum for a mask-less bn_bwd on zd."""
+    and both handles used, the two-BN bn_bwd_mask_join adds the two gradients
+    and runs both branches' backward on the masked sum in one reduce and one
+    apply."""
 
     @staticmethod
     def forward(ctx, z, zd, weight, bias, running_mean, running_var, momentum,
@@ -176,12 +177,11 @@ class _FusedBNAddBNFunction(torch.autograd.Function):
                 return (None,) * 17
         dy = _nhwc_grad(dy)
         if dy_b is not None:
-            dz, dw, db, dym = ops_api.ext().bn_bwd_mask_join(
-                z, dy, _nhwc_grad(dy_b), mask, sm, sr, weight, ctx.ws_bwd)
-            # dym is masked already; y is not read when relu is off
-            dzd, dw_d, db_d = ops_api.ext().bn_bwd(
-                zd, dym, dym, sm_d, sr_d, weight_d, False, False,
-                ctx.ws_bwd_d)
+            # the two-BN signature: one reduce forms the masked sum and the
+            # sums of both branches, one apply reads it for dz and dzd
+            dz, dw, db, _, dzd, dw_d, db_d = ops_api.ext().bn_bwd_mask_join(
+                z, dy, _nhwc_grad(dy_b), mask, sm, sr, weight, ctx.ws_bwd,
+                zd, sm_d, sr_d, weight_d, ctx.ws_bwd_d)
         else:
             bwd = ops_api.ext().bn_bwd_mask
             dz, dw, db = bwd(z, dy, mask, sm, sr, weight, True, False,

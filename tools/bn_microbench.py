@@ -25,7 +25,8 @@ counted there.
 --ab also times the `add` and `add_bn` tails with the block-output gradient
 arriving as two addends, as it does inside the network ("join"): once through
 the two-handle tails (forward_add_pair / forward_add_bn_pair: the add happens
-in bn_bwd_reduce_join, the apply reads its dz) and once through the
+in bn_bwd_reduce_join, the apply reads its dz; the add_bn tail runs both of
+its BNs through bn_bwd_reduce_join2 and bn_bwd_apply2) and once through the
 single-handle tails, where autograd adds the two gradients with a stand-alone
 kernel first and backward is bn_bwd_mask (with dres for `add`). The last
 table weights these by the 15 block boundaries of ResNet-50 that have two
@@ -66,8 +67,9 @@ BF16_ADD = "CUDAFunctor_add<c10::BFloat16>"
 FAMILIES = ["bn_fwd_reduce", "bn_fwd_finalize", "bn_fwd_apply",
             "bn_fwd_pool_apply", "bn_fwd_apply_add_bn",
             "max_pool_forward_nhwc",
-            "bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_finalize",
-            "bn_bwd_apply", "max_pool_backward_nhwc", BF16_ADD, "other"]
+            "bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_reduce_join2",
+            "bn_bwd_finalize", "bn_bwd_apply", "bn_bwd_apply2",
+            "max_pool_backward_nhwc", BF16_ADD, "other"]
 ROTATE_BYTES = 1 << 30
 
 
@@ -149,25 +151,32 @@ def expected_launches(kind, split):
 def join_bytes(kind, n_elem, C, gm_rows, pair):
     """family_bytes for a tail whose dy arrives as two addends. pair: the
     join reduce reads x and both addends and writes dz, the apply reads x and
-    dz; for add_bn the downsample branch then runs the mask-less backward on
-    dz. Otherwise torch's add (two reads, one write) comes first and backward
-    is the single-gradient one, which reads the mask in reduce and apply and,
-    for `add`, writes dres."""
+    dz; for add_bn one reduce reads z, zd and both addends and writes dz (and
+    three partial matrices, not two), and one apply reads z, zd and dz and
+    writes both dx. Otherwise torch's add (two reads, one write) comes first
+    and backward is the single-gradient one, which reads the mask in reduce
+    and apply and, for `add`, writes dres."""
     e, mask, part = 2 * n_elem, n_elem // 8, 2 * gm_rows * C * 4
     out = family_bytes(kind, n_elem, C, gm_rows, True)
-    two = 2 if kind == "add_bn" else 1
     if not pair:
         out[BF16_ADD] = 3 * e
         return out
-    out["bn_bwd_reduce_join"] = 4 * e + mask + part
-    out["bn_bwd_reduce"] = (two - 1) * (2 * e + part)
-    out["bn_bwd_apply"] = two * 3 * e
+    out["bn_bwd_reduce"] = out["bn_bwd_apply"] = 0
+    if kind == "add_bn":
+        out["bn_bwd_reduce_join2"] = 5 * e + mask + part * 3 // 2
+        out["bn_bwd_apply2"] = 5 * e
+    else:
+        out["bn_bwd_reduce_join"] = 4 * e + mask + part
+        out["bn_bwd_apply"] = 3 * e
     return out
 
 
 def join_launches(kind, pair):
     n = expected_launches(kind, False)
-    if pair:
+    if pair and kind == "add_bn":
+        n["bn_bwd_reduce_join2"] = n["bn_bwd_apply2"] = 1
+        n["bn_bwd_reduce"] = n["bn_bwd_apply"] = 0
+    elif pair:
         n["bn_bwd_reduce_join"] = 1
         n["bn_bwd_reduce"] -= 1
     else:
@@ -412,8 +421,8 @@ def main():
     gbs = [sum(join_bytes_sum[p].values()) / 1e9 for p in ("split", "fused")]
     print(f"{'sum':>24} {tot[0]:8.3f} {gbs[0]:7.2f} {'':>6} | "
           f"{tot[1]:8.3f} {gbs[1]:7.2f}")
-    bwd = ("bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_apply",
-           BF16_ADD)
+    bwd = ("bn_bwd_reduce", "bn_bwd_reduce_join", "bn_bwd_reduce_join2",
+           "bn_bwd_apply", "bn_bwd_apply2", BF16_ADD)
     tb = [sum(join_us[p][f] for f in bwd) / 1e3 for p in ("split", "fused")]
     print(f"{'backward streams only':>24} {tb[0]:8.3f} {'':>14} | {tb[1]:8.3f}")
 

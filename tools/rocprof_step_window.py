@@ -19,8 +19,8 @@ import sys
 
 FAMILIES = ["bn_fwd_reduce", "bn_fwd_finalize", "bn_fwd_apply",
             "bn_fwd_pool_apply", "bn_fwd_apply_add_bn", "bn_bwd_reduce",
-            "bn_bwd_reduce_join", "bn_bwd_finalize", "bn_bwd_apply",
-            "max_pool_forward_nhwc", "max_pool_backward_nhwc"]
+            "bn_bwd_reduce_join", "bn_bwd_reduce_join2", "bn_bwd_finalize",
+            "bn_bwd_apply", "bn_bwd_apply2", "max_pool_forward_nhwc", "max_pool_backward_nhwc"]
 # listed beside the BN kernels, not counted among them
 ADD = "CUDAFunctor_add<c10::BFloat16>"
 
