@@ -50,6 +50,7 @@ class ENV(enum.Enum):
     AUTODIST_RESOURCE_SPEC = ((lambda v: v or ""),)                 # path to resource spec yaml
     AUTODIST_SPARSE_PS_ROUTING = ((lambda v: v or "replicated"),)   # PS builders' default sparse_routing ("replicated" | "owner")
     AUTODIST_DENSE_AR_SCHEDULE = ((lambda v: v or "allreduce"),)    # AllReduce/Parallax builders' default schedule ("allreduce" | "sharded")
+    AUTODIST_VOCAB_CE = ((lambda v: v or "hip"),)                   # sharded vocab-parallel CE: "hip" kernels where eligible | "torch" forces the elementwise chain (A/B runs only)
 
     @property
     def val(self):

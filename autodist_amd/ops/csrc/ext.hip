@@ -1377,6 +1377,108 @@ torch::Tensor ce_bwd(torch::Tensor logits, torch::Tensor targets,
   return dlogits;
 }
 
+// ---- vocab-sharded cross-entropy (ce_ops.hip) ----
+
+// logits shard [N, V] bf16, unit column stride, row stride ld >= V
+static void ce_shard_check(const torch::Tensor& logits,
+                           const torch::Tensor& targets, long row_start) {
+  TORCH_CHECK(logits.is_cuda() && logits.dim() == 2 &&
+              logits.scalar_type() == torch::kBFloat16,
+              "ce_shard: logits must be a 2-D bf16 GPU tensor");
+  long N = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(V >= 1 && V < (1L << 31), "ce_shard: 1 <= V_r < 2^31");
+  TORCH_CHECK(N == 0 || (logits.stride(1) == 1 && logits.stride(0) >= V),
+              "ce_shard: logits rows must be contiguous (stride(1) == 1, "
+              "stride(0) >= V_r)");
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == torch::kLong &&
+              targets.dim() == 1 && targets.size(0) == N &&
+              targets.is_contiguous(),
+              "ce_shard: targets must be a contiguous int64 GPU vector [N]");
+  TORCH_CHECK(row_start >= 0, "ce_shard: row_start must be >= 0");
+}
+
+static void ce_shard_check_rowvec(const torch::Tensor& t, long N,
+                                  const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+              t.dim() == 1 && t.size(0) == N && t.is_contiguous(),
+              "ce_shard: ", name, " must be a contiguous fp32 GPU vector [N]");
+}
+
+static bool ce_shard_vec_ok(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+         t.stride(0) % CE_VEC == 0;
+}
+
+torch::Tensor ce_shard_stats(torch::Tensor logits, torch::Tensor targets,
+                             long row_start) {
+  ce_shard_check(logits, targets, row_start);
+  long N = logits.size(0), V = logits.size(1);
+  auto stats = torch::empty({3, N}, logits.options().dtype(torch::kFloat32));
+  if (N == 0) return stats;
+  TORCH_CHECK(N < (1L << 31), "ce_shard: N < 2^31");
+  long ld = logits.stride(0);
+  auto kern = ce_shard_vec_ok(logits) ? ce_shard_stats_kernel<true>
+                                      : ce_shard_stats_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(N), dim3(256), 0, cur_stream(),
+                     reinterpret_cast<__hip_bfloat16*>(logits.data_ptr()),
+                     targets.data_ptr<long>(), stats.data_ptr<float>(), N, V,
+                     ld, row_start);
+  return stats;
+}
+
+std::vector<torch::Tensor> ce_shard_combine(torch::Tensor stats_all) {
+  TORCH_CHECK(stats_all.is_cuda() && stats_all.dim() == 3 &&
+              stats_all.size(0) >= 1 && stats_all.size(1) == 3 &&
+              stats_all.scalar_type() == torch::kFloat32 &&
+              stats_all.is_contiguous(),
+              "ce_shard_combine: stats must be contiguous fp32 [world, 3, N] "
+              "on the GPU");
+  long world = stats_all.size(0), N = stats_all.size(2);
+  auto loss_rows = torch::empty({N}, stats_all.options());
+  auto lse2 = torch::empty({N}, stats_all.options());
+  if (N == 0) return {loss_rows, lse2};
+  hipLaunchKernelGGL(ce_shard_combine_kernel, dim3((N + 255) / 256),
+                     dim3(256), 0, cur_stream(), stats_all.data_ptr<float>(),
+                     loss_rows.data_ptr<float>(), lse2.data_ptr<float>(), N,
+                     (int)world);
+  return {loss_rows, lse2};
+}
+
+std::vector<torch::Tensor> ce_shard_bwd(torch::Tensor logits,
+                                        torch::Tensor targets, long row_start,
+                                        torch::Tensor lse2,
+                                        torch::Tensor dloss_rows) {
+  ce_shard_check(logits, targets, row_start);
+  long N = logits.size(0), V = logits.size(1);
+  ce_shard_check_rowvec(lse2, N, "lse2");
+  ce_shard_check_rowvec(dloss_rows, N, "dloss_rows");
+  auto fopt = logits.options().dtype(torch::kFloat32);
+  if (N == 0)
+    return {torch::empty({0, V}, logits.options()), torch::zeros({V}, fopt)};
+  // dlogits keeps the logits' row stride (padding columns are never written)
+  long ld = logits.stride(0);
+  auto dlogits = torch::empty({N, ld}, logits.options()).slice(1, 0, V);
+  long nstrips = (V + CE_STRIP_COLS - 1) / CE_STRIP_COLS;
+  long nchunks = (N + CE_BWD_ROWS - 1) / CE_BWD_ROWS;
+  TORCH_CHECK(nchunks <= 65535, "ce_shard_bwd: N <= 65535 * ", CE_BWD_ROWS);
+  long Vpad = nstrips * CE_STRIP_COLS;
+  auto partials = torch::empty({nchunks, Vpad}, fopt);
+  auto dbias = torch::empty({V}, fopt);
+  bool vec = ce_shard_vec_ok(logits) && ce_shard_vec_ok(dlogits) &&
+             reinterpret_cast<uintptr_t>(partials.data_ptr()) % 16 == 0;
+  auto kern = vec ? ce_shard_bwd_kernel<true> : ce_shard_bwd_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(nstrips, nchunks), dim3(256), 0, cur_stream(),
+                     reinterpret_cast<__hip_bfloat16*>(logits.data_ptr()),
+                     targets.data_ptr<long>(), lse2.data_ptr<float>(),
+                     dloss_rows.data_ptr<float>(),
+                     reinterpret_cast<__hip_bfloat16*>(dlogits.data_ptr()),
+                     partials.data_ptr<float>(), N, V, ld, row_start, Vpad);
+  hipLaunchKernelGGL(ce_shard_dbias_kernel, dim3((V + 255) / 256), dim3(256),
+                     0, cur_stream(), partials.data_ptr<float>(),
+                     dbias.data_ptr<float>(), V, Vpad, nchunks);
+  return {dlogits, dbias};
+}
+
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B, long cand) {
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && A.numel() == 16 * 32);
   TORCH_CHECK(B.scalar_type() == torch::kBFloat16 && B.numel() == 32 * 16);
@@ -1474,6 +1576,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ce_fwd", &ce_fwd,
         "fused online-softmax cross-entropy fwd -> loss_rows, m, l2s");
   m.def("ce_bwd", &ce_bwd, "fused cross-entropy bwd -> dlogits (bf16)");
+  m.def("ce_shard_stats", &ce_shard_stats,
+        "vocab-sharded CE: (logits [N, V_r] bf16, targets, row_start) -> "
+        "fp32 [3, N] local max, sum-exp, target logit");
+  m.def("ce_shard_combine", &ce_shard_combine,
+        "vocab-sharded CE: gathered stats [world, 3, N] -> (loss_rows, "
+        "lse2), summed in rank order");
+  m.def("ce_shard_bwd", &ce_shard_bwd,
+        "vocab-sharded CE: (logits, targets, row_start, lse2, dloss_rows) "
+        "-> (dlogits bf16 with the logits' row stride, dbias fp32 [V_r])");
+  // ce_shard_bwd tiling: columns per strip, rows per chunk
+  m.attr("CE_STRIP_COLS") = CE_STRIP_COLS;
+  m.attr("CE_BWD_ROWS") = CE_BWD_ROWS;
   m.def("col_sum", &col_sum, "bf16 [N,H] column sum -> fp32 [H]");
   m.def("ln_fwd", &ln_fwd,
         "fused bf16 LayerNorm(+residual) forward -> y, u, mean, rstd");

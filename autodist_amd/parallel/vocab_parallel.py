@@ -12,9 +12,11 @@ and never materializes full [N, V] logits on any GPU:
     one shard for input lookup and output projection),
   * each rank computes its logits shard [N, V_r] with one local GEMM
     (hipBLASLt bf16 under autocast),
-  * the softmax statistics cross ranks with THREE tiny collectives
-    (max, sum-exp, target-logit — all [N] floats over xGMI), instead of
-    all-gathering [N, V] logits,
+  * the softmax statistics cross ranks as ONE all-gather of packed [3, N]
+    floats (max, sum-exp, target-logit) on the bf16 GPU path, whose
+    streaming passes over the shard are the ce_shard_* HIP kernels; the
+    torch chain (CPU/gloo, fp32) uses three [N] all-reduces. Neither
+    all-gathers [N, V] logits,
   * the backward is shard-local for dW/db (rows are exclusively owned —
     no gradient sync, optimizer state naturally sharded) plus one
     all-reduce of dHidden [N, D].
@@ -113,6 +115,103 @@ class _VocabParallelCE(torch.autograd.Function):
                 None, None, None, None, None)
 
 
+def _use_hip_ce(hidden: torch.Tensor) -> bool:
+    """Selection rule of the sharded path: the gfx950 kernels serve bf16
+    compute (bf16 autocast, or a bf16 `hidden` without autocast) on the
+    GPU. CPU tensors are answered before anything touches the extension.
+    AUTODIST_VOCAB_CE=torch forces the elementwise chain (A/B runs only)."""
+    if not hidden.is_cuda:
+        return False
+    from autodist_amd.const import ENV
+    if ENV.AUTODIST_VOCAB_CE.val == "torch":
+        return False
+    if torch.is_autocast_enabled():
+        # fp16 autocast stays on the torch chain, which computes in fp16
+        if torch.get_autocast_dtype("cuda") != torch.bfloat16:
+            return False
+    elif hidden.dtype != torch.bfloat16:
+        return False
+    from autodist_amd.ops import api as ops_api
+    return ops_api.has_gpu_ops()
+
+
+class _VocabParallelCEHip(torch.autograd.Function):
+    """Mean cross-entropy over vocab-sharded bf16 logits through the
+    ce_shard_* kernels (ops/csrc/ce_ops.hip): one streaming read of the
+    shard forward, one read + one write backward, ONE all-gather of packed
+    [3, N] row statistics, and the bias gradient out of the backward kernel.
+    Every dtype is pinned here, so backward() may run outside the autocast
+    block that the forward ran under."""
+
+    @staticmethod
+    def forward(ctx, hidden, shard_w, shard_b, targets, row_start, world,
+                group):
+        from autodist_amd.ops import api as ops_api
+        e = ops_api.ext()
+        h2 = hidden.reshape(-1, hidden.shape[-1]).to(torch.bfloat16)
+        n, v = h2.shape[0], shard_w.shape[0]
+        # row stride rounded up to 8 elements: every logits row starts 16 B
+        # aligned (the kernels' vector width) for any shard size. The bf16
+        # copy of the weight (and bias) is made ld rows long, the <= 7 extra
+        # rows zero, so ONE GEMM with the bias in its epilogue writes the
+        # contiguous [n, ld] buffer and the shard is its [:, :v] view.
+        # (addmm with out= that view is correct too, but expands the bias
+        # into it in a pass of its own first.)
+        ld = (v + 7) // 8 * 8
+        if ld == v:
+            w = shard_w.to(torch.bfloat16)
+            b = shard_b.to(torch.bfloat16) if shard_b is not None else None
+        else:
+            w = shard_w.new_empty((ld, shard_w.shape[1]),
+                                  dtype=torch.bfloat16)
+            w[:v].copy_(shard_w)
+            w[v:].zero_()
+            b = None
+            if shard_b is not None:
+                b = shard_b.new_zeros(ld, dtype=torch.bfloat16)
+                b[:v].copy_(shard_b)
+        with torch.autocast("cuda", enabled=False):
+            logits = torch.nn.functional.linear(h2, w, b)[:, :v]
+        t = targets.reshape(-1)
+        stats = e.ce_shard_stats(logits, t, row_start)
+        if world > 1 or _forced():
+            nranks = dist.get_world_size(group)
+            stats_all = torch.empty((nranks,) + tuple(stats.shape),
+                                    dtype=stats.dtype, device=stats.device)
+            dist.all_gather_into_tensor(stats_all, stats, group=group)
+        else:
+            stats_all = stats[None]
+        loss_rows, lse2 = e.ce_shard_combine(stats_all)
+        # the bf16 weight copy is kept for dH (100 MB at [99184, 512]) rather
+        # than cast from the fp32 parameter a second time in backward
+        ctx.save_for_backward(h2, w, logits, t, lse2)
+        ctx.weight_dtype = shard_w.dtype
+        ctx.row_start = row_start
+        ctx.bias_dtype = shard_b.dtype if shard_b is not None else None
+        ctx.world = world
+        ctx.group = group
+        ctx.hidden_shape = hidden.shape
+        ctx.hidden_dtype = hidden.dtype
+        return loss_rows.mean()
+
+    @staticmethod
+    def backward(ctx, dloss):
+        from autodist_amd.ops import api as ops_api
+        h2, w, logits, t, lse2 = ctx.saved_tensors
+        n, v = logits.shape
+        dloss_rows = (dloss.float() / n).expand(n).contiguous()
+        dlogits, dbias = ops_api.ext().ce_shard_bwd(
+            logits, t, ctx.row_start, lse2, dloss_rows)
+        with torch.autocast("cuda", enabled=False):
+            dw = dlogits.t() @ h2            # [V_r, D] exclusively owned
+            dh = dlogits @ w[:v]             # [N, D] needs cross-rank sum
+        if ctx.world > 1 or _forced():
+            dist.all_reduce(dh, op=dist.ReduceOp.SUM, group=ctx.group)
+        dh = dh.to(ctx.hidden_dtype).view(ctx.hidden_shape)
+        db = dbias.to(ctx.bias_dtype) if ctx.bias_dtype is not None else None
+        return dh, dw.to(ctx.weight_dtype), db, None, None, None, None
+
+
 class VocabParallelProjection(torch.nn.Module):
     """Row-sharded (vocab-dim) output projection with fused sharded CE.
 
@@ -180,6 +279,10 @@ class VocabParallelProjection(torch.nn.Module):
                     and ops_api.has_gpu_ops()):
                 return _FusedCERows.apply(logits.contiguous(), t).mean()
             return torch.nn.functional.cross_entropy(logits, t)
+        if _use_hip_ce(hidden):
+            return _VocabParallelCEHip.apply(
+                hidden, self.weight, self.bias, targets, self.row_start,
+                self.world_size, self.process_group)
         return _VocabParallelCE.apply(hidden, self.weight, self.bias,
                                       targets, self.row_start, self.row_end,
                                       self.world_size, self.process_group)
