@@ -10,6 +10,8 @@ per-shard all-reduce groups).
 import torch
 import torch.nn as nn
 
+from autodist_amd.ops.fused_lstm import can_use_fused_lstmp, fused_lstmp
+
 
 class LM1BModel(nn.Module):
     def __init__(self, vocab_size=793470, emb_dim=512, hidden=2048,
@@ -49,13 +51,18 @@ class LM1BModel(nn.Module):
 
     def _hidden(self, tokens, state=None):
         x = self.drop(self.emb(tokens))
-        # run the LSTM OUTSIDE autocast in fp32: the decomposed ROCm LSTM
+        # Under autocast on the GPU the LSTM runs on the fused bf16 LSTMP
+        # kernels (ops/fused_lstm.py) where they serve this module. Otherwise
+        # it runs OUTSIDE autocast in fp32: the decomposed ROCm LSTM
         # thrashes bf16<->fp32 casts around every pointwise op under
-        # autocast (~170 cast kernels/step measured); a clean fp32 pass is
-        # net faster and more precise. The projection/CE stay bf16.
+        # autocast (~170 cast kernels/step measured), so a clean fp32 pass
+        # is faster and more precise than stock bf16.
         if torch.is_autocast_enabled() and x.is_cuda:
-            with torch.autocast(device_type="cuda", enabled=False):
-                h, state = self.lstm(x.float(), state)
+            if can_use_fused_lstmp(x, self.lstm):
+                h, state = fused_lstmp(x, self.lstm, state)
+            else:
+                with torch.autocast(device_type="cuda", enabled=False):
+                    h, state = self.lstm(x.float(), state)
         else:
             h, state = self.lstm(x, state)
         return self.drop(h), state

@@ -12,6 +12,7 @@
 #include "attention_bwd.hip"
 #include "ln_ops.hip"
 #include "ce_ops.hip"
+#include "lstm_ops.hip"
 
 namespace {
 
@@ -1479,6 +1480,105 @@ std::vector<torch::Tensor> ce_shard_bwd(torch::Tensor logits,
   return {dlogits, dbias};
 }
 
+// ---- projected-LSTM cell kernels (lstm_ops.hip) ----
+
+// [rows, cols] matrix of `dtype` on the GPU: unit column stride, row stride
+// >= cols, base and rows 16-byte aligned
+static void lstmp_check_mat(const torch::Tensor& t, long rows, long cols,
+                            torch::ScalarType dtype, bool strided_rows,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.scalar_type() == dtype &&
+                  t.size(0) == rows && t.size(1) == cols,
+              "lstmp: ", name, " must be a [", rows, ", ", cols, "] ",
+              dtype, " GPU tensor, got ", t.sizes(), " ", t.scalar_type());
+  TORCH_CHECK(t.stride(1) == 1 && t.stride(0) >= cols,
+              "lstmp: ", name, " needs a contiguous last dimension");
+  TORCH_CHECK(strided_rows || t.stride(0) == cols || rows == 1,
+              "lstmp: ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                  (rows == 1 || t.stride(0) * t.element_size() % 16 == 0),
+              "lstmp: ", name, " rows must be 16-byte aligned");
+}
+
+static void lstmp_check_dims(long B, long H, long P) {
+  TORCH_CHECK(B >= 1 && B <= (1L << 20), "lstmp: 1 <= B <= 2^20, got ", B);
+  TORCH_CHECK(P >= 32 && P % 32 == 0 && P <= LSTMP_MAX_P,
+              "lstmp: P must be a multiple of 32 in [32, ", LSTMP_MAX_P,
+              "], got ", P);
+  TORCH_CHECK(H >= 16 && H % 16 == 0 && H <= (1L << 20),
+              "lstmp: H must be a multiple of 16 (at most 2^20), got ", H);
+}
+
+#define LSTMP_S(t) reinterpret_cast<short*>((t).data_ptr())
+
+// One forward step: (gx_t [B, 4H] bf16 row-strided, h_prev [B, P] bf16
+// row-strided, w_hh [4H, P] bf16, bias [4H] fp32, c_prev [B, H] fp32) ->
+// writes c_out [B, H] fp32, hc_out [B, H] bf16, gates_out [B, 4H] bf16.
+void lstmp_cell_fwd(torch::Tensor gx, torch::Tensor h_prev, torch::Tensor w_hh,
+                    torch::Tensor bias, torch::Tensor c_prev,
+                    torch::Tensor c_out, torch::Tensor hc_out,
+                    torch::Tensor gates_out) {
+  TORCH_CHECK(h_prev.dim() == 2 && c_prev.dim() == 2,
+              "lstmp_cell_fwd: h_prev [B, P] and c_prev [B, H] expected");
+  long B = h_prev.size(0), P = h_prev.size(1), H = c_prev.size(1);
+  lstmp_check_dims(B, H, P);
+  lstmp_check_mat(gx, B, 4 * H, torch::kBFloat16, true, "gx_t");
+  lstmp_check_mat(h_prev, B, P, torch::kBFloat16, true, "h_prev");
+  lstmp_check_mat(w_hh, 4 * H, P, torch::kBFloat16, false, "w_hh");
+  lstmp_check_mat(c_prev, B, H, torch::kFloat32, false, "c_prev");
+  lstmp_check_mat(c_out, B, H, torch::kFloat32, false, "c_out");
+  lstmp_check_mat(hc_out, B, H, torch::kBFloat16, false, "hc_out");
+  lstmp_check_mat(gates_out, B, 4 * H, torch::kBFloat16, false, "gates_out");
+  TORCH_CHECK(bias.is_cuda() && bias.scalar_type() == torch::kFloat32 &&
+                  bias.dim() == 1 && bias.size(0) == 4 * H &&
+                  bias.is_contiguous(),
+              "lstmp_cell_fwd: bias must be a contiguous fp32 GPU vector [4H]");
+  dim3 grid((H + LSTMP_TILE_H - 1) / LSTMP_TILE_H,
+            (B + LSTMP_TILE_B - 1) / LSTMP_TILE_B);
+  hipLaunchKernelGGL(lstmp_cell_fwd_kernel, grid, dim3(256),
+                     lstmp_lds_bytes((int)P, true), cur_stream(), LSTMP_S(gx),
+                     gx.stride(0), LSTMP_S(h_prev), h_prev.stride(0),
+                     LSTMP_S(w_hh), bias.data_ptr<float>(),
+                     c_prev.data_ptr<float>(), c_out.data_ptr<float>(),
+                     LSTMP_S(hc_out), LSTMP_S(gates_out), (int)B, (int)H,
+                     (int)P);
+}
+
+// One backward step: (dh_t [B, P] bf16 row-strided, w_hr [P, H] bf16, gates
+// [B, 4H] bf16, c_t, c_prev [B, H] fp32, dc_next [B, H] fp32 or None = 0) ->
+// writes dgates [B, 4H] bf16 row-strided and dc_prev [B, H] fp32. dc_prev
+// may be dc_next itself (each element is read and written by one lane).
+void lstmp_cell_bwd(torch::Tensor dh, torch::Tensor w_hr, torch::Tensor gates,
+                    torch::Tensor c_t, torch::Tensor c_prev,
+                    c10::optional<torch::Tensor> dc_next, torch::Tensor dgates,
+                    torch::Tensor dc_prev) {
+  TORCH_CHECK(dh.dim() == 2 && c_t.dim() == 2,
+              "lstmp_cell_bwd: dh_t [B, P] and c_t [B, H] expected");
+  long B = dh.size(0), P = dh.size(1), H = c_t.size(1);
+  lstmp_check_dims(B, H, P);
+  lstmp_check_mat(dh, B, P, torch::kBFloat16, true, "dh_t");
+  lstmp_check_mat(w_hr, P, H, torch::kBFloat16, false, "w_hr");
+  lstmp_check_mat(gates, B, 4 * H, torch::kBFloat16, false, "gates");
+  lstmp_check_mat(c_t, B, H, torch::kFloat32, false, "c_t");
+  lstmp_check_mat(c_prev, B, H, torch::kFloat32, false, "c_prev");
+  lstmp_check_mat(dgates, B, 4 * H, torch::kBFloat16, true, "dgates");
+  lstmp_check_mat(dc_prev, B, H, torch::kFloat32, false, "dc_prev");
+  const float* dcn = nullptr;
+  if (dc_next.has_value() && dc_next->defined()) {
+    lstmp_check_mat(*dc_next, B, H, torch::kFloat32, false, "dc_next");
+    dcn = dc_next->data_ptr<float>();
+  }
+  dim3 grid((H + LSTMP_TILE_H - 1) / LSTMP_TILE_H,
+            (B + LSTMP_TILE_B - 1) / LSTMP_TILE_B);
+  hipLaunchKernelGGL(lstmp_cell_bwd_kernel, grid, dim3(256),
+                     lstmp_lds_bytes((int)P, false), cur_stream(), LSTMP_S(dh),
+                     dh.stride(0), LSTMP_S(w_hr), LSTMP_S(gates),
+                     c_t.data_ptr<float>(), c_prev.data_ptr<float>(), dcn,
+                     LSTMP_S(dgates), dgates.stride(0),
+                     dc_prev.data_ptr<float>(), (int)B, (int)H, (int)P);
+}
+#undef LSTMP_S
+
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B, long cand) {
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && A.numel() == 16 * 32);
   TORCH_CHECK(B.scalar_type() == torch::kBFloat16 && B.numel() == 32 * 16);
@@ -1588,6 +1688,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   // ce_shard_bwd tiling: columns per strip, rows per chunk
   m.attr("CE_STRIP_COLS") = CE_STRIP_COLS;
   m.attr("CE_BWD_ROWS") = CE_BWD_ROWS;
+  m.def("lstmp_cell_fwd", &lstmp_cell_fwd,
+        "LSTMP cell step on bf16 MFMA: (gx_t, h_prev, w_hh, bias, c_prev, "
+        "c_out, hc_out, gates_out); writes the three outputs");
+  m.def("lstmp_cell_bwd", &lstmp_cell_bwd,
+        "LSTMP cell step backward: (dh_t, w_hr, gates, c_t, c_prev, dc_next "
+        "or None, dgates_out, dc_prev_out); writes the two outputs");
+  // lstmp tiling: hidden units / batch rows per workgroup, largest P
+  m.attr("LSTMP_TILE_H") = LSTMP_TILE_H;
+  m.attr("LSTMP_TILE_B") = LSTMP_TILE_B;
+  m.attr("LSTMP_MAX_P") = LSTMP_MAX_P;
   m.def("col_sum", &col_sum, "bf16 [N,H] column sum -> fp32 [H]");
   m.def("ln_fwd", &ln_fwd,
         "fused bf16 LayerNorm(+residual) forward -> y, u, mean, rstd");
