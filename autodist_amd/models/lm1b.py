@@ -11,14 +11,27 @@ import torch
 import torch.nn as nn
 
 from autodist_amd.ops.fused_lstm import can_use_fused_lstmp, fused_lstmp
+from autodist_amd.ops.sampled_softmax import (LogUniformSampler,
+                                              sampled_softmax_loss)
 
 
 class LM1BModel(nn.Module):
     def __init__(self, vocab_size=793470, emb_dim=512, hidden=2048,
                  layers=2, proj=512, dropout=0.1, tie_weights=True,
-                 sparse=False, sharded_softmax=False):
+                 sparse=False, sharded_softmax=False, num_sampled=0,
+                 sampler_seed=0):
         super().__init__()
         self.sharded_softmax = sharded_softmax
+        # num_sampled > 0: training uses the sampled softmax loss the
+        # reference trains with (language_model.py: sampled_softmax_loss,
+        # num_sampled = 8192); evaluation keeps the full softmax
+        if num_sampled > 0 and sharded_softmax:
+            raise ValueError("num_sampled > 0 with sharded_softmax=True: the "
+                             "vocab-parallel sampled softmax is not built")
+        self.num_sampled = num_sampled
+        self.sampler = (LogUniformSampler(vocab_size, num_sampled,
+                                          sampler_seed)
+                        if num_sampled > 0 else None)
         if sharded_softmax:
             # vocab-parallel path (reference partitioner seam,
             # partitioner.py:577-602): row-sharded tied table — input
@@ -79,6 +92,15 @@ class LM1BModel(nn.Module):
         if self.sharded_softmax:
             h, _ = self._hidden(tokens, state)
             return self.out.loss(h, targets)
+        if self.num_sampled > 0 and self.training:
+            h, _ = self._hidden(tokens, state)
+            h = h.reshape(-1, h.size(-1))
+            targets = targets.reshape(-1)
+            sampled, logq_samp = self.sampler.sample(h.device)
+            return sampled_softmax_loss(
+                h, self.out_weight, self.out_bias, targets, sampled,
+                self.sampler.logq_true(targets), logq_samp,
+                sparse_grad=self.emb.sparse)
         logits, _ = self.forward(tokens, state)
         return torch.nn.functional.cross_entropy(
             logits.reshape(-1, logits.size(-1)), targets.reshape(-1))

@@ -13,6 +13,7 @@
 #include "ln_ops.hip"
 #include "ce_ops.hip"
 #include "lstm_ops.hip"
+#include "ssm_ops.hip"
 
 namespace {
 
@@ -1579,6 +1580,168 @@ void lstmp_cell_bwd(torch::Tensor dh, torch::Tensor w_hr, torch::Tensor gates,
 }
 #undef LSTMP_S
 
+// ---- sampled softmax loss (ssm_ops.hip) ----
+
+// contiguous [rows, cols] GPU matrix of `dtype`, base and rows 16-byte aligned
+static void ssm_check_mat(const torch::Tensor& t, long rows, long cols,
+                          torch::ScalarType dtype, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.scalar_type() == dtype &&
+                  t.size(0) == rows && t.size(1) == cols,
+              "ssm: ", name, " must be a [", rows, ", ", cols, "] ", dtype,
+              " GPU tensor, got ", t.sizes(), " ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), "ssm: ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0 &&
+                  cols * t.element_size() % 16 == 0,
+              "ssm: ", name, " rows must be 16-byte aligned");
+}
+
+static void ssm_check_vec(const torch::Tensor& t, long n,
+                          torch::ScalarType dtype, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 1 && t.size(0) == n &&
+                  t.scalar_type() == dtype && t.is_contiguous(),
+              "ssm: ", name, " must be a contiguous ", dtype,
+              " GPU vector [", n, "], got ", t.sizes(), " ", t.scalar_type());
+}
+
+static void ssm_check_dims(long N, long S, long P) {
+  TORCH_CHECK(P >= 32 && P % 32 == 0 && P <= SSM_MAX_P,
+              "ssm: P must be a multiple of 32 in [32, ", SSM_MAX_P,
+              "], got ", P);
+  TORCH_CHECK(S >= 1 && S <= (1L << 24), "ssm: 1 <= S <= 2^24, got ", S);
+  TORCH_CHECK(N >= 1 && N <= (1L << 24), "ssm: 1 <= N <= 2^24, got ", N);
+}
+
+static long ssm_pad(long S) { return (S + SSM_BN - 1) / SSM_BN * SSM_BN; }
+
+#define SSM_S(t) reinterpret_cast<short*>((t).data_ptr())
+
+// (table [V, P] fp32 or bf16, bias [V] fp32 or None, sampled [S], targets
+// [N], logq_samp [S], logq_true [N]) -> Wg [S_pad, P] bf16, Wt [N, P] bf16,
+// off [S_pad], off0 [N]. Ids within [0, V) are the caller's contract.
+std::vector<torch::Tensor> ssm_prep(torch::Tensor table,
+                                    c10::optional<torch::Tensor> bias,
+                                    torch::Tensor sampled,
+                                    torch::Tensor targets,
+                                    torch::Tensor logq_samp,
+                                    torch::Tensor logq_true) {
+  TORCH_CHECK(table.dim() == 2 && sampled.dim() == 1 && targets.dim() == 1,
+              "ssm_prep: table [V, P], sampled [S], targets [N] expected");
+  long V = table.size(0), P = table.size(1);
+  long S = sampled.size(0), N = targets.size(0);
+  ssm_check_dims(N, S, P);
+  TORCH_CHECK(V >= 1 && V < (1L << 31), "ssm_prep: 1 <= V < 2^31");
+  bool f32 = table.scalar_type() == torch::kFloat32;
+  ssm_check_mat(table, V, P, f32 ? torch::kFloat32 : torch::kBFloat16,
+                "table (fp32 or bf16)");
+  ssm_check_vec(sampled, S, torch::kLong, "sampled");
+  ssm_check_vec(targets, N, torch::kLong, "targets");
+  ssm_check_vec(logq_samp, S, torch::kFloat32, "logq_samp");
+  ssm_check_vec(logq_true, N, torch::kFloat32, "logq_true");
+  const float* bp = nullptr;
+  if (bias.has_value() && bias->defined()) {
+    ssm_check_vec(*bias, V, torch::kFloat32, "bias");
+    bp = bias->data_ptr<float>();
+  }
+  long S_pad = ssm_pad(S);
+  auto bopt = table.options().dtype(torch::kBFloat16);
+  auto fopt = table.options().dtype(torch::kFloat32);
+  auto wg = torch::empty({S_pad, P}, bopt), wt = torch::empty({N, P}, bopt);
+  auto off = torch::empty({S_pad}, fopt), off0 = torch::empty({N}, fopt);
+  long items = (S_pad + N) * (P / 8);
+  dim3 grid((unsigned)((items + 255) / 256));
+#define SSM_PREP_ARGS                                                      \
+  bp, sampled.data_ptr<long>(), targets.data_ptr<long>(),                  \
+      logq_samp.data_ptr<float>(), logq_true.data_ptr<float>(), SSM_S(wg), \
+      SSM_S(wt), off.data_ptr<float>(), off0.data_ptr<float>(), (int)S,    \
+      (int)S_pad, (int)N, (int)P
+  if (f32)
+    hipLaunchKernelGGL(ssm_prep_kernel<float>, grid, dim3(256), 0,
+                       cur_stream(), table.data_ptr<float>(), SSM_PREP_ARGS);
+  else
+    hipLaunchKernelGGL(ssm_prep_kernel<short>, grid, dim3(256), 0,
+                       cur_stream(), SSM_S(table), SSM_PREP_ARGS);
+#undef SSM_PREP_ARGS
+  return {wg, wt, off, off0};
+}
+
+// shared operand checks of the forward and the backward; returns S_pad
+static long ssm_check_main(const torch::Tensor& h, const torch::Tensor& wg,
+                           const torch::Tensor& off,
+                           const torch::Tensor& sampled,
+                           const torch::Tensor& targets) {
+  TORCH_CHECK(h.dim() == 2 && sampled.dim() == 1,
+              "ssm: h [N, P] and sampled [S] expected");
+  long N = h.size(0), P = h.size(1), S = sampled.size(0);
+  ssm_check_dims(N, S, P);
+  long S_pad = ssm_pad(S);
+  ssm_check_mat(h, N, P, torch::kBFloat16, "h");
+  ssm_check_mat(wg, S_pad, P, torch::kBFloat16, "Wg");
+  ssm_check_vec(off, S_pad, torch::kFloat32, "off");
+  ssm_check_vec(sampled, S, torch::kLong, "sampled");
+  ssm_check_vec(targets, N, torch::kLong, "targets");
+  return S_pad;
+}
+
+// -> loss [N], lse2 [N] (log2 domain), z0 [N], all fp32
+std::vector<torch::Tensor> ssm_fwd(torch::Tensor h, torch::Tensor wg,
+                                   torch::Tensor wt, torch::Tensor off,
+                                   torch::Tensor off0, torch::Tensor sampled,
+                                   torch::Tensor targets) {
+  long S_pad = ssm_check_main(h, wg, off, sampled, targets);
+  long N = h.size(0), P = h.size(1), S = sampled.size(0);
+  ssm_check_mat(wt, N, P, torch::kBFloat16, "Wt");
+  ssm_check_vec(off0, N, torch::kFloat32, "off0");
+  long splits = (S_pad + SSM_SPLIT_COLS - 1) / SSM_SPLIT_COLS;
+  auto fopt = h.options().dtype(torch::kFloat32);
+  auto part = torch::empty({splits, N, 2}, fopt);
+  auto loss = torch::empty({N}, fopt), lse2 = torch::empty({N}, fopt);
+  auto z0 = torch::empty({N}, fopt);
+  dim3 grid((unsigned)((N + SSM_BM - 1) / SSM_BM), (unsigned)splits);
+  hipLaunchKernelGGL(ssm_fwd_kernel, grid, dim3(256), 0, cur_stream(),
+                     SSM_S(h), SSM_S(wg), SSM_S(wt), off.data_ptr<float>(),
+                     off0.data_ptr<float>(), sampled.data_ptr<long>(),
+                     targets.data_ptr<long>(), part.data_ptr<float>(),
+                     z0.data_ptr<float>(), (int)N, (int)S, (int)S_pad, (int)P);
+  hipLaunchKernelGGL(ssm_combine_kernel, dim3((unsigned)((N + 255) / 256)),
+                     dim3(256), 0, cur_stream(), part.data_ptr<float>(),
+                     z0.data_ptr<float>(), loss.data_ptr<float>(),
+                     lse2.data_ptr<float>(), (int)N, (int)splits);
+  return {loss, lse2, z0};
+}
+
+// g [N] is the incoming gradient of loss -> dz [N, S_pad] bf16, dz0 [N] fp32,
+// db_samp [S] fp32 (column sums of the unrounded dz)
+std::vector<torch::Tensor> ssm_bwd(torch::Tensor h, torch::Tensor wg,
+                                   torch::Tensor off, torch::Tensor sampled,
+                                   torch::Tensor targets, torch::Tensor lse2,
+                                   torch::Tensor z0, torch::Tensor g) {
+  long S_pad = ssm_check_main(h, wg, off, sampled, targets);
+  long N = h.size(0), P = h.size(1), S = sampled.size(0);
+  ssm_check_vec(lse2, N, torch::kFloat32, "lse2");
+  ssm_check_vec(z0, N, torch::kFloat32, "z0");
+  ssm_check_vec(g, N, torch::kFloat32, "g");
+  long splits = (S_pad + SSM_SPLIT_COLS - 1) / SSM_SPLIT_COLS;
+  long row_blocks = (N + SSM_BM - 1) / SSM_BM;
+  auto fopt = h.options().dtype(torch::kFloat32);
+  auto dz = torch::empty({N, S_pad}, h.options());
+  auto colpart = torch::empty({row_blocks, S_pad}, fopt);
+  auto dz0 = torch::empty({N}, fopt), db = torch::empty({S}, fopt);
+  hipLaunchKernelGGL(ssm_bwd_kernel, dim3((unsigned)row_blocks,
+                                          (unsigned)splits),
+                     dim3(256), 0, cur_stream(), SSM_S(h), SSM_S(wg),
+                     off.data_ptr<float>(), sampled.data_ptr<long>(),
+                     targets.data_ptr<long>(), lse2.data_ptr<float>(),
+                     z0.data_ptr<float>(), g.data_ptr<float>(), SSM_S(dz),
+                     colpart.data_ptr<float>(), dz0.data_ptr<float>(), (int)N,
+                     (int)S, (int)S_pad, (int)P);
+  hipLaunchKernelGGL(ssm_dbias_kernel, dim3((unsigned)((S + 255) / 256)),
+                     dim3(256), 0, cur_stream(), colpart.data_ptr<float>(),
+                     db.data_ptr<float>(), (int)S, (int)S_pad,
+                     (int)row_blocks);
+  return {dz, dz0, db};
+}
+#undef SSM_S
+
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B, long cand) {
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && A.numel() == 16 * 32);
   TORCH_CHECK(B.scalar_type() == torch::kBFloat16 && B.numel() == 32 * 16);
@@ -1698,6 +1861,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("LSTMP_TILE_H") = LSTMP_TILE_H;
   m.attr("LSTMP_TILE_B") = LSTMP_TILE_B;
   m.attr("LSTMP_MAX_P") = LSTMP_MAX_P;
+  m.def("ssm_prep", &ssm_prep,
+        "sampled softmax: (table, bias or None, sampled, targets, logq_samp, "
+        "logq_true) -> (Wg [S_pad, P] bf16, Wt [N, P] bf16, off, off0)");
+  m.def("ssm_fwd", &ssm_fwd,
+        "sampled softmax forward on bf16 MFMA: (h, Wg, Wt, off, off0, "
+        "sampled, targets) -> (loss [N], lse2 [N], z0 [N])");
+  m.def("ssm_bwd", &ssm_bwd,
+        "sampled softmax backward: (h, Wg, off, sampled, targets, lse2, z0, "
+        "g) -> (dz [N, S_pad] bf16, dz0 [N], db_samp [S])");
+  // ssm tiling: rows per block, columns per tile / per split, largest P
+  m.attr("SSM_BM") = SSM_BM;
+  m.attr("SSM_BN") = SSM_BN;
+  m.attr("SSM_SPLIT_COLS") = SSM_SPLIT_COLS;
+  m.attr("SSM_MAX_P") = SSM_MAX_P;
   m.def("col_sum", &col_sum, "bf16 [N,H] column sum -> fp32 [H]");
   m.def("ln_fwd", &ln_fwd,
         "fused bf16 LayerNorm(+residual) forward -> y, u, mean, rstd");

@@ -30,6 +30,10 @@ def main():
     parser.add_argument("--sharded-softmax", action="store_true",
                         help="vocab-parallel tied projection + sharded CE "
                              "(parallel/vocab_parallel.py)")
+    parser.add_argument("--num-sampled", type=int, default=0,
+                        help="train with the sampled softmax loss over this "
+                             "many log-uniform candidates (the reference "
+                             "uses 8192); 0 keeps the full softmax")
     parser.add_argument("--small", action="store_true",
                         help="10k-vocab model (CPU-sized)")
     args = parser.parse_args()
@@ -38,7 +42,8 @@ def main():
     ad = AutoDist(strategy_builder=getattr(strat, args.autodist_strategy)())
     with ad.scope():
         torch.manual_seed(0)
-        kw = {"sharded_softmax": args.sharded_softmax}
+        kw = {"sharded_softmax": args.sharded_softmax,
+              "num_sampled": args.num_sampled}
         model = lm1b_small(**kw) if args.small else lm1b_full(**kw)
         optimizer = torch.optim.Adagrad(model.parameters(), lr=0.01)
     vocab = model.emb.num_embeddings
