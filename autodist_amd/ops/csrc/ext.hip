@@ -14,6 +14,7 @@
 #include "ce_ops.hip"
 #include "lstm_ops.hip"
 #include "ssm_ops.hip"
+#include "ncf_ops.hip"
 
 namespace {
 
@@ -1742,6 +1743,205 @@ std::vector<torch::Tensor> ssm_bwd(torch::Tensor h, torch::Tensor wg,
 }
 #undef SSM_S
 
+// ---- fused NeuMF (ncf_ops.hip) ----
+
+static void neumf_check_f32(const torch::Tensor& t, const torch::Tensor& ids,
+                            const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ids.device() &&
+                  t.scalar_type() == torch::kFloat32 && t.is_contiguous(),
+              "neumf: ", name, " must be a contiguous fp32 tensor on the ids' "
+              "GPU, got ", t.sizes(), " ", t.scalar_type());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "neumf: ",
+              name, " must be 16-byte aligned");
+}
+
+static void neumf_check_width(long w, const char* name) {
+  TORCH_CHECK(w >= 8 && w <= NEUMF_MAX_WIDTH && w % 8 == 0, "neumf: ", name,
+              " must be a multiple of 8 in [8, ", NEUMF_MAX_WIDTH, "], got ",
+              w);
+}
+
+static const float* neumf_opt_rows(const c10::optional<torch::Tensor>& t,
+                                   const torch::Tensor& ids,
+                                   const char* name) {
+  if (!t.has_value() || !t->defined()) return nullptr;
+  neumf_check_f32(*t, ids, name);
+  TORCH_CHECK(t->dim() == 1 && t->size(0) == ids.size(0), "neumf: ", name,
+              " must be [B]");
+  return t->data_ptr<float>();
+}
+
+// Checks every operand and fills the kernel arguments; nothing is launched
+// when a check fails. tables = (mf_user, mf_item, mlp_user, mlp_item).
+static NeumfArgs neumf_args(const torch::Tensor& users,
+                            const torch::Tensor& items,
+                            const std::vector<torch::Tensor>& tables,
+                            const std::vector<torch::Tensor>& weights,
+                            const std::vector<torch::Tensor>& biases,
+                            const torch::Tensor& w_head,
+                            const torch::Tensor& b_head,
+                            const c10::optional<torch::Tensor>& labels,
+                            const c10::optional<torch::Tensor>& weight) {
+  TORCH_CHECK(users.is_cuda() && users.dim() == 1 &&
+                  users.scalar_type() == torch::kLong &&
+                  users.is_contiguous() && items.is_cuda() &&
+                  items.device() == users.device() && items.dim() == 1 &&
+                  items.scalar_type() == torch::kLong &&
+                  items.is_contiguous() && items.size(0) == users.size(0),
+              "neumf: users and items must be contiguous int64 GPU vectors of "
+              "one length");
+  long B = users.size(0);
+  TORCH_CHECK(B >= 1 && B <= (1L << 30), "neumf: 1 <= B <= 2^30, got ", B);
+  TORCH_CHECK(tables.size() == 4, "neumf: four tables expected");
+  const char* tn[4] = {"mf_user", "mf_item", "mlp_user", "mlp_item"};
+  for (int i = 0; i < 4; ++i) {
+    neumf_check_f32(tables[i], users, tn[i]);
+    TORCH_CHECK(tables[i].dim() == 2 && tables[i].size(0) >= 1 &&
+                    tables[i].size(0) < (1L << 31),
+                "neumf: ", tn[i], " must be [rows, D] with 1 <= rows < 2^31");
+  }
+  long mf = tables[0].size(1), E = tables[2].size(1);
+  TORCH_CHECK(tables[1].size(1) == mf && tables[3].size(1) == E &&
+                  tables[2].size(0) == tables[0].size(0) &&
+                  tables[3].size(0) == tables[1].size(0),
+              "neumf: the user tables and the item tables must agree in rows, "
+              "the mf tables and the mlp tables in width");
+  neumf_check_width(mf, "mf_dim");
+  neumf_check_width(2 * E, "the MLP input width");
+  long L = (long)weights.size();
+  TORCH_CHECK(L >= 1 && L <= NEUMF_MAX_LAYERS && (long)biases.size() == L,
+              "neumf: 1 to ", NEUMF_MAX_LAYERS,
+              " MLP layers with a bias each expected, got ", L);
+  NeumfArgs a = {};
+  a.users = users.data_ptr<long>();
+  a.items = items.data_ptr<long>();
+  a.mf_user = tables[0].data_ptr<float>();
+  a.mf_item = tables[1].data_ptr<float>();
+  a.mlp_user = tables[2].data_ptr<float>();
+  a.mlp_item = tables[3].data_ptr<float>();
+  a.num_users = tables[0].size(0);
+  a.num_items = tables[1].size(0);
+  a.B = (int)B;
+  a.mf = (int)mf;
+  a.E = (int)E;
+  a.L = (int)L;
+  NeumfLayer* ls[NEUMF_MAX_LAYERS] = {&a.l1, &a.l2, &a.l3, &a.l4};
+  long K = 2 * E, act = 0, P = 0;
+  for (long l = 0; l < L; ++l) {
+    const torch::Tensor& W = weights[l];
+    neumf_check_f32(W, users, "an MLP weight");
+    neumf_check_f32(biases[l], users, "an MLP bias");
+    TORCH_CHECK(W.dim() == 2 && W.size(1) == K && biases[l].dim() == 1 &&
+                    biases[l].size(0) == W.size(0),
+                "neumf: MLP layer ", l + 1, " must be [N, ", K,
+                "] with bias [N], got ", W.sizes(), " and ",
+                biases[l].sizes());
+    long N = W.size(0);
+    neumf_check_width(N, "an MLP width");
+    NeumfLayer& ly = *ls[l];
+    ly.W = W.data_ptr<float>();
+    ly.b = biases[l].data_ptr<float>();
+    ly.K = (int)K;
+    ly.N = (int)N;
+    ly.in_off = (int)(act - K);  // column of H_{l-1}; unused for l = 1
+    ly.out_off = (int)act;
+    ly.w_off = (int)P;
+    ly.b_off = (int)(P + N * K);
+    P += N * K + N;
+    act += N;
+    K = N;
+  }
+  a.l1.in_off = 0;
+  a.act_ld = (int)act;
+  a.wl = (int)K;
+  a.act_off_last = (int)(act - K);
+  a.head_off = (int)P;
+  a.P = (int)(P + mf + K + 1);
+  neumf_check_f32(w_head, users, "the head weight");
+  neumf_check_f32(b_head, users, "the head bias");
+  TORCH_CHECK(w_head.numel() == mf + K && b_head.numel() == 1,
+              "neumf: the head must be [1, ", mf + K, "] with one bias, got ",
+              w_head.sizes());
+  a.w_head = w_head.data_ptr<float>();
+  a.b_head = b_head.data_ptr<float>();
+  a.labels = neumf_opt_rows(labels, users, "labels");
+  a.weight = neumf_opt_rows(weight, users, "weight");
+  TORCH_CHECK(a.labels || !a.weight, "neumf: weight needs labels");
+  return a;
+}
+
+// (users [B], items [B], tables, MLP weights, MLP biases, head weight, head
+// bias, labels [B] or None, weight [B] or None, save_acts) -> (logits [B],
+// loss_rows [B] (empty without labels), acts [B, sum N_l] (empty unless
+// save_acts): the post-ReLU activations neumf_bwd reads)
+std::vector<torch::Tensor> neumf_fwd(torch::Tensor users, torch::Tensor items,
+                                     std::vector<torch::Tensor> tables,
+                                     std::vector<torch::Tensor> weights,
+                                     std::vector<torch::Tensor> biases,
+                                     torch::Tensor w_head, torch::Tensor b_head,
+                                     c10::optional<torch::Tensor> labels,
+                                     c10::optional<torch::Tensor> weight,
+                                     bool save_acts) {
+  NeumfArgs a = neumf_args(users, items, tables, weights, biases, w_head,
+                           b_head, labels, weight);
+  auto fopt = w_head.options();
+  auto logits = torch::empty({a.B}, fopt);
+  auto loss = torch::empty({a.labels ? a.B : 0}, fopt);
+  auto acts = torch::empty({save_acts ? a.B : 0, a.act_ld}, fopt);
+  unsigned tiles = (unsigned)((a.B + NEUMF_TILE - 1) / NEUMF_TILE);
+  hipLaunchKernelGGL(neumf_fwd_kernel, dim3(tiles), dim3(256), 0,
+                     cur_stream(), a, logits.data_ptr<float>(),
+                     a.labels ? loss.data_ptr<float>() : nullptr,
+                     save_acts ? acts.data_ptr<float>() : nullptr);
+  return {logits, loss, acts};
+}
+
+// (..., logits, acts of neumf_fwd, labels, weight, g_logits [B] or None,
+// g_loss [B] or None) -> (d_mf_user [B, mf], d_mf_item [B, mf], d_mlp_user
+// [B, E], d_mlp_item [B, E]: one row per sample, and the dense gradients as
+// one vector [P]: per layer dW_l [N_l, K_l] then db_l [N_l], then dw_head
+// [mf + N_L], db_head [1])
+std::vector<torch::Tensor> neumf_bwd(torch::Tensor users, torch::Tensor items,
+                                     std::vector<torch::Tensor> tables,
+                                     std::vector<torch::Tensor> weights,
+                                     std::vector<torch::Tensor> biases,
+                                     torch::Tensor w_head, torch::Tensor b_head,
+                                     torch::Tensor logits, torch::Tensor acts,
+                                     c10::optional<torch::Tensor> labels,
+                                     c10::optional<torch::Tensor> weight,
+                                     c10::optional<torch::Tensor> g_logits,
+                                     c10::optional<torch::Tensor> g_loss) {
+  NeumfArgs a = neumf_args(users, items, tables, weights, biases, w_head,
+                           b_head, labels, weight);
+  const float* zl = neumf_opt_rows(logits, users, "logits");
+  const float* gz = neumf_opt_rows(g_logits, users, "g_logits");
+  const float* gl = neumf_opt_rows(g_loss, users, "g_loss");
+  TORCH_CHECK(zl, "neumf_bwd: logits expected");
+  neumf_check_f32(acts, users, "acts");
+  TORCH_CHECK(acts.dim() == 2 && acts.size(0) == a.B &&
+                  acts.size(1) == a.act_ld,
+              "neumf_bwd: acts must be [", a.B, ", ", a.act_ld, "], got ",
+              acts.sizes());
+  auto fopt = w_head.options();
+  auto d_mfu = torch::empty({a.B, a.mf}, fopt);
+  auto d_mfi = torch::empty({a.B, a.mf}, fopt);
+  auto d_mlpu = torch::empty({a.B, a.E}, fopt);
+  auto d_mlpi = torch::empty({a.B, a.E}, fopt);
+  int tiles = (a.B + NEUMF_TILE - 1) / NEUMF_TILE;
+  int blocks = std::min(tiles, NEUMF_MAX_BWD_BLOCKS);
+  auto ws = torch::empty({blocks, a.P}, fopt);
+  auto dense = torch::empty({a.P}, fopt);
+  hipLaunchKernelGGL(neumf_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0,
+                     cur_stream(), a, zl, acts.data_ptr<float>(), gz, gl,
+                     d_mfu.data_ptr<float>(), d_mfi.data_ptr<float>(),
+                     d_mlpu.data_ptr<float>(), d_mlpi.data_ptr<float>(),
+                     ws.data_ptr<float>(), tiles);
+  hipLaunchKernelGGL(neumf_reduce_kernel, dim3((unsigned)((a.P + 255) / 256)),
+                     dim3(256), 0, cur_stream(), ws.data_ptr<float>(),
+                     dense.data_ptr<float>(), a.P, blocks);
+  return {d_mfu, d_mfi, d_mlpu, d_mlpi, dense};
+}
+
 torch::Tensor mfma_probe(torch::Tensor A, torch::Tensor B, long cand) {
   TORCH_CHECK(A.scalar_type() == torch::kBFloat16 && A.numel() == 16 * 32);
   TORCH_CHECK(B.scalar_type() == torch::kBFloat16 && B.numel() == 32 * 16);
@@ -1875,6 +2075,20 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("SSM_BN") = SSM_BN;
   m.attr("SSM_SPLIT_COLS") = SSM_SPLIT_COLS;
   m.attr("SSM_MAX_P") = SSM_MAX_P;
+  m.def("neumf_fwd", &neumf_fwd,
+        "fused NeuMF forward on fp32 MFMA: (users, items, [mf_user, mf_item, "
+        "mlp_user, mlp_item], MLP weights, MLP biases, head weight, head "
+        "bias, labels or None, weight or None, save_acts) -> (logits [B], "
+        "loss_rows [B], acts [B, sum N_l])");
+  m.def("neumf_bwd", &neumf_bwd,
+        "fused NeuMF backward: (the forward's operands up to the head bias, "
+        "logits, acts, labels or None, weight or None, g_logits or None, "
+        "g_loss or None) -> (d_mf_user, d_mf_item, d_mlp_user, d_mlp_item "
+        "rows [B, D], dense gradients [P])");
+  // neumf limits and tiling: layers, widest layer, samples per block
+  m.attr("NEUMF_MAX_LAYERS") = NEUMF_MAX_LAYERS;
+  m.attr("NEUMF_MAX_WIDTH") = NEUMF_MAX_WIDTH;
+  m.attr("NEUMF_TILE") = NEUMF_TILE;
   m.def("col_sum", &col_sum, "bf16 [N,H] column sum -> fp32 [H]");
   m.def("ln_fwd", &ln_fwd,
         "fused bf16 LayerNorm(+residual) forward -> y, u, mean, rstd");
