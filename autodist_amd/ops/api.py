@@ -323,3 +323,72 @@ def segment_coalesce(indices: torch.Tensor, values: torch.Tensor):
                       dtype=values.dtype, device=values.device)
     out.index_add_(0, inv, values)
     return uniq, out
+
+
+_COALESCE_WS = {}
+
+
+def _coalesce_workspace(device: torch.device, num_rows: int) -> torch.Tensor:
+    """Persistent int32 workspace of coalesce_rows_ranked for one table
+    height: bitmap | word prefix | block totals (ops/csrc/sparse_ops.hip).
+    The kernels leave the bitmap all-zero, so it is zeroed once, here. Keyed
+    by stream as well: two streams must not share a bitmap in flight."""
+    key = (device.index, int(num_rows),
+           torch.cuda.current_stream(device).cuda_stream)
+    ws = _COALESCE_WS.get(key)
+    if ws is None:
+        words = (int(num_rows) + 31) // 32
+        ws = torch.zeros(2 * words + (words + 255) // 256, dtype=torch.int32,
+                         device=device)
+        _COALESCE_WS[key] = ws
+    return ws
+
+
+def coalesce_rows_ranked(indices: torch.Tensor, values: torch.Tensor,
+                         num_rows: int, scale: float = 1.0,
+                         exact: bool = True):
+    """Sum the rows of `values` that share an id: sort-free and
+    bit-reproducible. `indices` [n] are int64 row ids in [0, num_rows).
+
+    Row s of the result is the sum of round_fp32(values[i] * scale) over the
+    inputs with the s-th smallest distinct id, added in ascending i starting
+    from the first addend: the bits of a sequential CPU loop, on every run.
+
+    exact=True  -> (uniq[m], out[m, ...]); one host read (the count), a
+                   drop-in for segment_coalesce.
+    exact=False -> (uniq[n], out[n, ...], count[1] int32) with no host
+                   synchronisation: uniq[m:] == -1 and out[m:] == 0, which
+                   fused_sparse_apply skips.
+
+    fp32 GPU values run the HIP kernels of ops/csrc/sparse_ops.hip; CPU
+    tensors, other dtypes and a missing extension take a torch composite
+    with the same results (torch.unique + CPU-order index_add_)."""
+    n = indices.shape[0]
+    if (indices.is_cuda and values.is_cuda and values.dtype == torch.float32
+            and indices.dtype == torch.int64 and indices.dim() == 1
+            and has_gpu_ops()):
+        ws = _coalesce_workspace(indices.device, num_rows)
+        uniq, out, count = ext().coalesce_rows_ranked(
+            indices.contiguous(), values.contiguous(), int(num_rows), ws,
+            float(scale))
+        if not exact:
+            return uniq, out, count
+        m = int(count.item())
+        return uniq[:m], out[:m]
+    # torch composite; the adds run on the CPU, where index_add_ is a
+    # sequential loop over the inputs
+    sv = (values if scale == 1.0 else values * scale).cpu()
+    uniq, inv = torch.unique(indices.cpu(), sorted=True, return_inverse=True)
+    m = uniq.shape[0]
+    out = torch.zeros((m,) + tuple(sv.shape[1:]), dtype=sv.dtype)
+    out.index_add_(0, inv, sv)
+    uniq, out = uniq.to(indices.device), out.to(values.device)
+    if exact:
+        return uniq, out
+    pad_u = torch.full((n,), -1, dtype=uniq.dtype, device=uniq.device)
+    pad_u[:m] = uniq
+    pad_o = torch.zeros((n,) + tuple(out.shape[1:]), dtype=out.dtype,
+                        device=out.device)
+    pad_o[:m] = out
+    count = torch.tensor([m], dtype=torch.int32, device=indices.device)
+    return pad_u, pad_o, count

@@ -15,6 +15,7 @@
 #include "lstm_ops.hip"
 #include "ssm_ops.hip"
 #include "ncf_ops.hip"
+#include "sparse_ops.hip"
 
 namespace {
 
@@ -1086,6 +1087,95 @@ void sparse_apply_rows(int64_t opt, torch::Tensor param, torch::Tensor rows,
   }
 }
 
+// Sort-free deterministic coalesce (see sparse_ops.hip). workspace is the
+// caller's persistent int32 buffer for this table height, bitmap part all
+// zero on entry and again on exit. Returns (uniq[n], out[n, D], count[1]),
+// padded; nothing here reads the device.
+std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> coalesce_rows_ranked(
+    torch::Tensor ids, torch::Tensor vals, int64_t num_rows,
+    torch::Tensor workspace, double scale) {
+  TORCH_CHECK(ids.is_cuda() && ids.scalar_type() == torch::kInt64 &&
+              ids.dim() == 1 && ids.is_contiguous(),
+              "ids must be a contiguous 1-D int64 GPU tensor");
+  check_f32_flat(vals, "vals");
+  TORCH_CHECK(num_rows >= 1 && num_rows < (1LL << 31),
+              "num_rows must be in [1, 2^31), got ", num_rows);
+  long n = ids.numel();
+  TORCH_CHECK(n < (1LL << 31), "at most 2^31 - 1 input rows");
+  TORCH_CHECK(vals.dim() >= 1 && vals.size(0) == n,
+              "vals must have one row per id");
+  long R = num_rows;
+  long W = (R + 31) / 32;
+  long nblk = (W + BLOCK_THREADS - 1) / BLOCK_THREADS;
+  TORCH_CHECK(workspace.is_cuda() && workspace.is_contiguous() &&
+              workspace.scalar_type() == torch::kInt32 &&
+              workspace.numel() >= 2 * W + nblk &&
+              workspace.device() == ids.device() &&
+              vals.device() == ids.device(),
+              "workspace must be an int32 tensor of 2*ceil(R/32) + "
+              "ceil(ceil(R/32)/256) words on the ids' device");
+  auto iopt = ids.options();
+  auto uniq = torch::empty({n}, iopt);
+  auto out = torch::empty_like(vals);
+  if (n == 0)
+    return {uniq, out, torch::zeros({1}, iopt.dtype(torch::kInt32))};
+  long D = vals.numel() / n;
+  TORCH_CHECK(D > 0, "vals rows must not be empty");
+  auto count = torch::empty({1}, iopt.dtype(torch::kInt32));
+  auto scratch = torch::empty({4 * n + 1}, iopt.dtype(torch::kInt32));
+  int* ws = workspace.data_ptr<int>();
+  unsigned int* bitmap = reinterpret_cast<unsigned int*>(ws);
+  int* prefix = ws + W;
+  int* blocksum = ws + 2 * W;
+  int* sc = scratch.data_ptr<int>();
+  int* slot = sc;
+  int* cnt = sc + n;
+  int* start = sc + 2 * n;
+  int* perm = sc + 3 * n;
+  int* cursor = sc + 4 * n;
+  int* cp = count.data_ptr<int>();
+  const int64_t* ip = ids.data_ptr<int64_t>();
+  const float* vp = vals.data_ptr<float>();
+  float* op = out.data_ptr<float>();
+  int64_t* up = uniq.data_ptr<int64_t>();
+  hipStream_t st = cur_stream();
+  dim3 blk(BLOCK_THREADS);
+  dim3 grid_n(grid_for(n, 1));
+  dim3 grid_w((unsigned)std::min<long>(nblk, 65535L * 8));
+  hipLaunchKernelGGL(coalesce_mark_kernel, grid_n, blk, 0, st, ip, bitmap,
+                     cnt, cursor, n, R);
+  hipLaunchKernelGGL(coalesce_totals_kernel, grid_w, blk, 0, st, bitmap,
+                     blocksum, W);
+  hipLaunchKernelGGL(coalesce_scan_kernel, dim3(1), blk, 0, st, blocksum, cp,
+                     nblk);
+  hipLaunchKernelGGL(coalesce_emit_kernel, grid_w, blk, 0, st, bitmap,
+                     blocksum, prefix, up, W, n);
+  hipLaunchKernelGGL(coalesce_count_kernel, grid_n, blk, 0, st, ip, bitmap,
+                     prefix, slot, cnt, n, R);
+  hipLaunchKernelGGL(coalesce_alloc_kernel, grid_n, blk, 0, st, cnt, start,
+                     cursor, cp, n);
+  hipLaunchKernelGGL(coalesce_place_kernel, grid_n, blk, 0, st, ip, slot,
+                     start, perm, bitmap, n);
+  bool vec4 = D % 4 == 0 && aligned16(vp) && aligned16(op);
+  long chunks = vec4 ? D / 4 : D;
+  int log2_group = 0;
+  while (log2_group < 6 && (1L << log2_group) < chunks) ++log2_group;
+  long rows_per_block = BLOCK_THREADS >> log2_group;
+  long blocks = (n + rows_per_block - 1) / rows_per_block;
+  if (blocks > 65535L * 8) blocks = 65535L * 8;
+  dim3 grid_s((unsigned)blocks);
+  if (vec4) {
+    hipLaunchKernelGGL((coalesce_sum_kernel<4>), grid_s, blk, 0, st, vp, slot,
+                       cnt, start, perm, cp, op, up, n, D, log2_group,
+                       (float)scale);
+  } else {
+    hipLaunchKernelGGL((coalesce_sum_kernel<1>), grid_s, blk, 0, st, vp, slot,
+                       cnt, start, perm, cp, op, up, n, D, log2_group,
+                       (float)scale);
+  }
+  return {uniq, out, count};
+}
+
 // ------------------------------------------------------------- PowerSGD
 torch::Tensor psgd_mq(torch::Tensor M2d, torch::Tensor Qp) {
   long n = M2d.size(0), s = M2d.size(1);
@@ -1985,6 +2075,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "dedup-sum row-sparse gradient");
   m.def("scatter_add_rows", &scatter_add_rows, "rowwise scatter-add");
   m.def("gather_rows", &gather_rows, "rowwise gather");
+  m.def("coalesce_rows_ranked", &coalesce_rows_ranked,
+        "sort-free deterministic coalesce of row-sparse gradients: "
+        "(uniq[n], out[n, D], count[1]), padded, no host read");
   m.def("sparse_apply_rows", &sparse_apply_rows,
         "fused row-wise SGD/Adagrad/Adam update of unique rows (gfx950)");
   m.def("bn_fwd_train", &bn_fwd_train,

@@ -8,7 +8,8 @@ one small int64 allgather + one large padded allgather). The variable-length
 all-to-all (alltoallv) serves ShardedEmbedding's id/vector exchange and the
 owner-routed sparse PS push.
 """
-from typing import List, Tuple
+import os
+from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
@@ -106,15 +107,31 @@ def alltoallv(parts, world, group, trailing_shape=(), recv_sizes=None):
     return [out[offs[r]:offs[r + 1]] for r in range(world)], recv_list
 
 
-def coalesce_rows(indices: torch.Tensor, values: torch.Tensor
+def coalesce_rows(indices: torch.Tensor, values: torch.Tensor,
+                  num_rows: Optional[int] = None,
+                  scale: Optional[float] = None
                   ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Sum duplicate rows (the reference's sparse-accumulator dedup,
-    ps_synchronizer.py:498-535). On gfx950 the segmented-reduce HIP kernel
-    (ops/csrc/sparse_ops.hip) replaces the sort+index_add composite."""
+    ps_synchronizer.py:498-535); the unique ids come out ascending.
+
+    With `num_rows` (the table height) fp32 GPU values go through the
+    sort-free HIP kernels of ops/csrc/sparse_ops.hip: duplicates are added
+    in input order, so the result is bit-reproducible, and `scale` is applied
+    to every row inside the kernel. Without `num_rows`, or with
+    AUTODIST_SPARSE_COALESCE=unique, the GPU path is segment_coalesce
+    (a device sort for the dedup, float atomics for the sum) and `scale` is
+    a separate multiply in front of it."""
     if indices.numel() == 0:
-        return indices, values
+        return indices, values if scale is None else values * scale
     from autodist_amd.ops import api as ops_api
-    if ops_api.has_gpu_ops() and indices.is_cuda:
+    on_gpu = ops_api.has_gpu_ops() and indices.is_cuda
+    if (on_gpu and num_rows is not None and values.dtype == torch.float32
+            and os.environ.get("AUTODIST_SPARSE_COALESCE", "") != "unique"):
+        return ops_api.coalesce_rows_ranked(
+            indices, values, num_rows, 1.0 if scale is None else scale)
+    if scale is not None:
+        values = values * scale
+    if on_gpu:
         return ops_api.segment_coalesce(indices, values)
     uniq, inv = torch.unique(indices, sorted=True, return_inverse=True)
     out = torch.zeros((uniq.shape[0],) + tuple(values.shape[1:]),

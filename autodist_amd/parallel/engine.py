@@ -775,7 +775,7 @@ class DistributedEngine:
             # use the RAW (possibly duplicated) rows: torch's coalesce() is
             # a full sort pass (rocprim radix/merge sorts were 37% of the
             # NCF step, measured), and rows dedup ONCE anyway in
-            # coalesce_rows (segment-coalesce HIP kernel) after the gather
+            # coalesce_rows (sort-free HIP kernels, sparse_ops.hip) after the gather
             indices, values = grad._indices()[0], grad._values()
         else:
             # dense grad on a sparse-flagged var: treat all rows as touched
@@ -788,17 +788,7 @@ class DistributedEngine:
         if grad is None:
             return
         indices, values = self._sparse_grad_rows(grad)
-        # weight BEFORE the gather so uneven batch splits produce the exact
-        # weighted average after cross-rank coalesce (c0.py:92-119 semantics)
-        values = values * self.grad_scale()
-        if self.collectives_active:
-            idx_parts, val_parts, sizes = allgather_rows(
-                indices, values, self.world_size, self.process_group,
-                force=self._force_collectives)
-            self._sparse_rows_received += sum(sizes) - sizes[self.rank]
-            indices, values = torch.cat(idx_parts), torch.cat(val_parts)
-        indices, values = coalesce_rows(indices, values)
-        # replicated rowwise apply: identical on every rank == PS result
+        nrows = plan.param.shape[0]
         sh = plan.shards[0]
         if sh.state is None:
             sh.state = apply_mod.make_state(plan.cls_name, plan.param.data,
@@ -806,8 +796,46 @@ class DistributedEngine:
         cls = plan.cls_name
         if cls == "Adam" and plan.hyper.get("_sparse_adam"):
             cls = "SparseAdam"
+        if self.collectives_active:
+            # weight BEFORE the gather so uneven batch splits produce the
+            # exact weighted average after cross-rank coalesce (c0.py:92-119
+            # semantics)
+            values = values * self.grad_scale()
+            idx_parts, val_parts, sizes = allgather_rows(
+                indices, values, self.world_size, self.process_group,
+                force=self._force_collectives)
+            self._sparse_rows_received += sum(sizes) - sizes[self.rank]
+            indices, values = torch.cat(idx_parts), torch.cat(val_parts)
+            indices, values = coalesce_rows(indices, values, num_rows=nrows)
+        elif self._ranked_coalesce_ok(cls, indices, values):
+            # no host read at all: the padded pair goes straight into the
+            # row-wise apply kernel, which skips the -1 pad ids
+            from autodist_amd.ops import api as ops_api
+            indices, values, count = ops_api.coalesce_rows_ranked(
+                indices, values, nrows, self.grad_scale(), exact=False)
+            if ops_api.fused_sparse_apply(cls, plan.param.data, indices,
+                                          values, sh.state, plan.hyper):
+                return
+            m = int(count.item())
+            indices, values = indices[:m], values[:m]
+        else:
+            # the weight moves into the coalesce kernel's scale
+            indices, values = coalesce_rows(indices, values, num_rows=nrows,
+                                            scale=self.grad_scale())
+        # replicated rowwise apply: identical on every rank == PS result
         apply_mod.apply_sparse_rows(cls, plan.param.data, indices, values,
                                     sh.state, plan.hyper)
+
+    @staticmethod
+    def _ranked_coalesce_ok(cls, indices, values) -> bool:
+        """Sync-free coalesce + fused apply: the optimizer classes
+        fused_sparse_apply serves, fp32 rows on the GPU, and the sort-free
+        coalesce not switched off."""
+        from autodist_amd.ops import api as ops_api
+        return (cls in ops_api._SPARSE_FUSED_IDS and indices.is_cuda
+                and indices.numel() > 0 and values.dtype == torch.float32
+                and os.environ.get("AUTODIST_SPARSE_COALESCE", "") != "unique"
+                and ops_api.has_gpu_ops())
 
     def _sync_and_apply_sparse_routed(self, plan: VarPlan):
         """Owner-routed sparse PS round: push rows to their shard owners,
@@ -826,8 +854,8 @@ class DistributedEngine:
         indices, values = self._sparse_grad_rows(grad)
         # 1) weight (uneven batch splits), then dedup locally so each rank
         #    pushes a row at most once; coalesced ids come out sorted
-        values = values * self.grad_scale()
-        indices, values = coalesce_rows(indices, values)
+        indices, values = coalesce_rows(indices, values, num_rows=nrows,
+                                        scale=self.grad_scale())
         # 2) push: sorted ids make every shard one contiguous segment; a
         #    rank's part is the concatenation of the segments it owns
         if plan.shard_edges is None:
@@ -861,7 +889,8 @@ class DistributedEngine:
         #    not: its step counter is the global step (Adagrad lr_decay, Adam
         #    bias correction), exactly as the replicated path advances it.
         own_ids, own_vals = coalesce_rows(torch.cat(recv_ids),
-                                          torch.cat(recv_vals))
+                                          torch.cat(recv_vals),
+                                          num_rows=nrows)
         own_vals = own_vals.contiguous()
         new_rows = torch.empty_like(own_vals)
         cls = plan.cls_name
