@@ -9,6 +9,7 @@
 #include "psgd_gemm.hip"
 #include "mfma_probe.hip"
 #include "attention.hip"
+#include "attention_split.hip"
 #include "attention_bwd.hip"
 #include "ln_ops.hip"
 #include "ce_ops.hip"
@@ -1285,6 +1286,73 @@ torch::Tensor attn_fwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   return o;
 }
 
+// Split-KV forward (attention_split.hip): kv_splits workgroups share the keys
+// of one (b, h, query block), a second kernel merges their partial softmaxes.
+// The count is clamped to ATTN_MAX_SPLITS and to the T = ceil(S / 64) tiles,
+// and the effective count ceil(T / ceil(T / n)) leaves no split empty, so
+// every workgroup's first tile starts below S. p_drop exists to be refused:
+// dropout stays on attn_fwd.
+torch::Tensor attn_fwd_split(torch::Tensor q, torch::Tensor k,
+                             torch::Tensor v, double scale,
+                             c10::optional<torch::Tensor> mask,
+                             int64_t kv_splits, double p_drop = 0.0) {
+  TORCH_CHECK(p_drop == 0.0, "attn_fwd_split has no dropout; use attn_fwd");
+  TORCH_CHECK(kv_splits >= 1, "kv_splits must be >= 1, got ", kv_splits);
+  TORCH_CHECK(q.dim() == 4 && (q.size(3) == 64 || q.size(3) == 128),
+              "attn_fwd_split expects [B,H,S,64|128]");
+  long D = q.size(3);
+  attn_check_strided(q, D, "q");
+  attn_check_strided(k, D, "k");
+  attn_check_strided(v, D, "v");
+  long B = q.size(0), H = q.size(1), S = q.size(2);
+  TORCH_CHECK(S % 32 == 0 && S >= 32, "S must be a multiple of 32");
+  TORCH_CHECK(k.sizes() == q.sizes() && v.sizes() == q.sizes());
+  long nbh = B * H;
+  long T = (S + 63) / 64;
+  long n = std::min<long>(std::min<long>(kv_splits, ATTN_MAX_SPLITS), T);
+  long tps = (T + n - 1) / n;
+  n = (T + tps - 1) / tps;
+  auto o = torch::empty({B, H, S, D}, q.options());
+  auto f32 = q.options().dtype(torch::kFloat32);
+  auto o_part = torch::empty({n, nbh, S, D}, f32);
+  auto ml_part = torch::empty({2, n, nbh, S}, f32);
+  float* m_part = ml_part.data_ptr<float>();
+  float* l_part = m_part + n * nbh * S;
+  auto launch = [&](auto kern, long rows) {
+    long nqb = (S + rows - 1) / rows;
+    TORCH_CHECK(n * nqb * nbh < (1L << 31), "attn_fwd_split: grid too large");
+    hipLaunchKernelGGL(kern, dim3(n * nqb * nbh), dim3(256), 0, cur_stream(),
+                       reinterpret_cast<__hip_bfloat16*>(q.data_ptr()),
+                       reinterpret_cast<__hip_bfloat16*>(k.data_ptr()),
+                       reinterpret_cast<__hip_bfloat16*>(v.data_ptr()),
+                       o_part.data_ptr<float>(), m_part, l_part,
+                       attn_mask_ptr(mask, B, S), S, H, nbh, nqb, tps,
+                       q.stride(0), q.stride(1), q.stride(2),
+                       k.stride(0), k.stride(1), k.stride(2),
+                       v.stride(0), v.stride(1), v.stride(2), (float)scale);
+  };
+  auto combine = [&](auto kern, long rows_per_block) {
+    long rows = nbh * S;
+    hipLaunchKernelGGL(kern,
+                       dim3((rows + rows_per_block - 1) / rows_per_block),
+                       dim3(256), 0, cur_stream(), o_part.data_ptr<float>(),
+                       m_part, l_part,
+                       reinterpret_cast<__hip_bfloat16*>(o.data_ptr()), rows,
+                       (int)n);
+  };
+  // RB as attn_fwd picks it
+  if (D == 64) {
+    if (S >= 256) launch(attn_fwd_split_kernel<2, 64>, 128);
+    else launch(attn_fwd_split_kernel<1, 64>, 64);
+    combine(attn_fwd_combine_kernel<64>, 256 / (64 / 8));
+  } else {
+    if (S >= 256) launch(attn_fwd_split_kernel<2, 128>, 128);
+    else launch(attn_fwd_split_kernel<1, 128>, 64);
+    combine(attn_fwd_combine_kernel<128>, 256 / (128 / 8));
+  }
+  return o;
+}
+
 torch::Tensor attn_dropmask(long B, long H, long S, double p_drop,
                             int64_t seed, torch::Device dev) {
   auto out = torch::empty({B, H, S, S},
@@ -2195,6 +2263,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
         py::arg("mask") = py::none(), py::arg("p_drop") = 0.0,
         py::arg("seed") = 0);
+  m.def("attn_fwd_split", &attn_fwd_split,
+        "split-KV MFMA attention forward: partial-softmax kernel over "
+        "kv_splits key ranges + combine (no dropout)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("mask") = py::none(), py::arg("kv_splits") = 1,
+        py::arg("p_drop") = 0.0);
+  m.attr("ATTN_MAX_SPLITS") = (int)ATTN_MAX_SPLITS;
   m.def("attn_bwd", &attn_bwd,
         "fused MFMA attention backward (GPU-validated) -> dq, dk, dv",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"),

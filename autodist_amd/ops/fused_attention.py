@@ -10,8 +10,15 @@ BERT/transformer hot path for both serving and training. Dropout uses a
 counter-based hash of (seed, bh, q, k) regenerated identically in the
 backward (flash-attention style, no S x S state); the seed is drawn
 host-side per forward call.
+
+Without dropout the forward also exists as a split-KV variant
+(ops/csrc/attention_split.hip): `kv_splits` workgroups share the keys of one
+query block and a combine kernel merges their partial softmaxes. It is chosen
+by `fused_sdpa(..., kv_splits=n)`, by AUTODIST_ATTN_KV_SPLITS, or by
+`auto_kv_splits` where the one-kernel grid leaves most of the GPU idle.
 """
 import math
+import os
 import random
 from typing import Optional
 
@@ -77,10 +84,57 @@ def can_use_fused(q, attn_mask, dropout_p, k=None, v=None) -> bool:
     return _mask_rows(attn_mask, q) is not None
 
 
+ATTN_MAX_SPLITS = 8    # csrc/attention_split.hip
+# Grid-fill level of the dispatch rule, in workgroups per CU: the split path
+# is chosen while the one-kernel grid nqb * B * H is below
+# SPLIT_FILL * multi_processor_count. Measured on MI355X (profiles/
+# ANALYSIS.md, "Split-KV attention forward"): grids of 48, 96 and 128
+# workgroups on 256 CUs are faster split, 192 and above are not; D = 128 was
+# measured only at a grid that loses, so the rule takes D = 64 alone.
+SPLIT_FILL = 0.75
+
+
+def auto_kv_splits(B, H, S, D, n_cu, fill=None) -> int:
+    """Split count the dispatch rule picks for a dropout-free forward, 0 for
+    the one-kernel path. Splitting pays an fp32 write and read of
+    splits x |O|, so it is chosen only where the grid is the problem:
+    S >= 512 (the regime where the one-kernel forward was measured behind)
+    and fewer than fill * n_cu workgroups. The count is the smallest that
+    reaches that level, capped at ATTN_MAX_SPLITS and at half the 64-key
+    tiles (a split keeps at least two tiles, so its double buffer overlaps
+    a load with compute)."""
+    fill = SPLIT_FILL if fill is None else fill
+    if S < 512 or D != 64:
+        return 0
+    grid = -(-S // 128) * B * H          # RB = 2 from S >= 256
+    want = fill * n_cu
+    if grid >= want:
+        return 0
+    n = min(math.ceil(want / grid), ATTN_MAX_SPLITS, -(-S // 64) // 2)
+    return n if n >= 2 else 0
+
+
+def _env_kv_splits() -> int:
+    """AUTODIST_ATTN_KV_SPLITS: unset or 0 = dispatch rule, 1 = never split,
+    n = force n splits."""
+    raw = os.environ.get("AUTODIST_ATTN_KV_SPLITS", "0") or "0"
+    n = int(raw)
+    if n < 0:
+        raise ValueError(f"AUTODIST_ATTN_KV_SPLITS must be >= 0, got {raw}")
+    return n
+
+
 class FusedAttentionFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, scale, mask, p_drop, seed):
-        o = ops_api.ext().attn_fwd(q, k, v, scale, mask, p_drop, seed)
+    def forward(ctx, q, k, v, scale, mask, p_drop, seed, kv_splits=0):
+        # kv_splits >= 1: split-KV forward (p_drop == 0 only; the binding
+        # refuses anything else). The backward recomputes m and l from q
+        # and k and needs only the saved o, so it is the same either way.
+        if kv_splits:
+            o = ops_api.ext().attn_fwd_split(q, k, v, scale, mask,
+                                             kv_splits, p_drop)
+        else:
+            o = ops_api.ext().attn_fwd(q, k, v, scale, mask, p_drop, seed)
         ctx.save_for_backward(q, k, v, o, *([mask] if mask is not None
                                             else []))
         ctx.scale = scale
@@ -98,22 +152,45 @@ class FusedAttentionFn(torch.autograd.Function):
         dq, dk, dv = ops_api.ext().attn_bwd(q, k, v, o, dout.contiguous(),
                                             ctx.scale, mask, ctx.p_drop,
                                             ctx.seed)
-        return dq, dk, dv, None, None, None, None
+        return dq, dk, dv, None, None, None, None, None
 
 
 def fused_sdpa(q, k, v, attn_mask: Optional[torch.Tensor] = None,
-               dropout_p: float = 0.0, scale: Optional[float] = None):
+               dropout_p: float = 0.0, scale: Optional[float] = None,
+               kv_splits: Optional[int] = None):
     """Drop-in for torch SDPA on [B, H, S, D] tensors.
+
+    kv_splits: an integer >= 1 forces the split-KV forward with that many
+    key ranges (1 included: bit-equal to the one-kernel forward); it needs
+    dropout_p == 0. None leaves the choice to AUTODIST_ATTN_KV_SPLITS and
+    then to `auto_kv_splits`. Ignored where the fused kernels do not apply.
 
     Note: dropout_p is applied only in training-style calls; callers pass
     0.0 for eval (as the models do). The dropout mask differs from torch's
     RNG but is a valid iid Bernoulli(1-p) mask with exact fwd/bwd
     consistency.
     """
+    if kv_splits is not None:
+        if kv_splits < 1:
+            raise ValueError(f"kv_splits must be >= 1, got {kv_splits}")
+        if dropout_p > 0.0:
+            raise ValueError("kv_splits needs dropout_p == 0: the split-KV "
+                             "forward has no dropout")
     if scale is None:
         scale = 1.0 / math.sqrt(q.size(-1))
     if can_use_fused(q, attn_mask, dropout_p, k, v):
         mask = _key_padding_mask(attn_mask, q)
+        splits = 0
+        if kv_splits is not None:
+            splits = int(kv_splits)
+        elif dropout_p == 0.0:
+            env = _env_kv_splits()
+            if env >= 2:
+                splits = env
+            elif env == 0:
+                splits = auto_kv_splits(
+                    *q.shape, torch.cuda.get_device_properties(
+                        q.device).multi_processor_count)
         seed = random.getrandbits(31) if dropout_p > 0.0 else 0
         # kernels are stride-aware in B/H/S (head dim must be contiguous):
         # transposed views of the fused qkv projection pass through with
@@ -121,6 +198,6 @@ def fused_sdpa(q, k, v, attn_mask: Optional[torch.Tensor] = None,
         def _ok(t):
             return t if t.stride(-1) == 1 else t.contiguous()
         return FusedAttentionFn.apply(_ok(q), _ok(k), _ok(v), scale, mask,
-                                      float(dropout_p), seed)
+                                      float(dropout_p), seed, splits)
     return torch.nn.functional.scaled_dot_product_attention(
         q, k, v, attn_mask=attn_mask, dropout_p=dropout_p, scale=scale)
