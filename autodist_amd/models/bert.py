@@ -7,8 +7,11 @@ masked-LM head (weight-tied). BASELINE config #3 is BERT-base Parallax on
 8x MI355X: dense params sync over bucketed RCCL all-reduce, the (sparse)
 embedding tables go to load-balanced PS owners.
 
-Attention uses torch.scaled_dot_product_attention (ROCm SDPA); params stay
-fp32 with bf16 autocast compute.
+Attention runs the fused MFMA kernels (ops/fused_attention.py; torch SDPA
+where they do not apply), LayerNorm and the Linear bias gradients their HIP
+kernels, and the masked-LM loss the fused linear + cross-entropy kernels
+(ops/fused_linear_ce.py), which compute only the labelled positions and
+never store the logits. Params stay fp32 with bf16 autocast compute.
 """
 
 import torch
@@ -19,7 +22,14 @@ from autodist_amd.ops.fused_linear import FusedLinear, fused_linear
 
 class BertConfig:
     def __init__(self, vocab_size=30522, hidden=768, layers=12, heads=12,
-                 intermediate=3072, max_seq=512, type_vocab=2, dropout=0.1):
+                 intermediate=3072, max_seq=512, type_vocab=2, dropout=0.1,
+                 max_predictions=None):
+        # the data pipeline's max_predictions_per_seq; None: no bound. The
+        # MLM loss uses it as ONE bound for the batch, not per sequence: of
+        # the labelled positions of a batch, in input order, those past the
+        # first batch * max_predictions are dropped (data that keeps to the
+        # per-sequence bound never reaches it).
+        self.max_predictions = max_predictions
         self.vocab_size = vocab_size
         self.hidden = hidden
         self.layers = layers
@@ -131,19 +141,38 @@ class BertForPreTraining(nn.Module):
         self.mlm_bias = nn.Parameter(torch.zeros(cfg.vocab_size))
         self.nsp = FusedLinear(cfg.hidden, 2)
 
-    def forward(self, input_ids, token_type_ids=None, attention_mask=None):
+    def _heads(self, input_ids, token_type_ids, attention_mask):
+        """MLM transform output m [B, S, H] (the input of the tied output
+        projection) and the NSP logits."""
         h = self.bert(input_ids, token_type_ids, attention_mask)
         m = self.mlm_ln(torch.nn.functional.gelu(self.mlm_dense(h)))
+        return m, self.nsp(h[:, 0])
+
+    def forward(self, input_ids, token_type_ids=None, attention_mask=None):
+        m, nsp = self._heads(input_ids, token_type_ids, attention_mask)
         logits = fused_linear(m, self.bert.tok_emb.weight, self.mlm_bias)
-        nsp = self.nsp(h[:, 0])
         return logits, nsp
 
     def loss(self, input_ids, mlm_labels, nsp_labels=None,
              token_type_ids=None, attention_mask=None):
-        logits, nsp = self.forward(input_ids, token_type_ids, attention_mask)
-        l = torch.nn.functional.cross_entropy(
-            logits.view(-1, logits.size(-1)), mlm_labels.view(-1),
-            ignore_index=-100)
+        from autodist_amd.ops.fused_linear_ce import (
+            can_use_lce_kernels, fused_linear_cross_entropy)
+        m, nsp = self._heads(input_ids, token_type_ids, attention_mask)
+        table = self.bert.tok_emb.weight
+        mp = self.bert.cfg.max_predictions
+        if mp is not None or can_use_lce_kernels(m, table, self.mlm_bias):
+            # the kernels: only the labelled positions, logits never stored.
+            # With a bound set the op also serves the steps the kernels do
+            # not (captured, fp32, CPU), by its torch composite, so every
+            # step drops the same positions past the bound.
+            l = fused_linear_cross_entropy(
+                m, table, self.mlm_bias, mlm_labels,
+                max_rows=None if mp is None else input_ids.size(0) * mp)
+        else:
+            logits = fused_linear(m, table, self.mlm_bias)
+            l = torch.nn.functional.cross_entropy(
+                logits.view(-1, logits.size(-1)), mlm_labels.view(-1),
+                ignore_index=-100)
         if nsp_labels is not None:
             l = l + torch.nn.functional.cross_entropy(nsp, nsp_labels)
         return l

@@ -15,6 +15,7 @@
 #include "ce_ops.hip"
 #include "lstm_ops.hip"
 #include "ssm_ops.hip"
+#include "lce_ops.hip"
 #include "ncf_ops.hip"
 #include "sparse_ops.hip"
 
@@ -1901,6 +1902,175 @@ std::vector<torch::Tensor> ssm_bwd(torch::Tensor h, torch::Tensor wg,
 }
 #undef SSM_S
 
+// ---- fused linear + cross-entropy (lce_ops.hip) ----
+
+static void lce_check_vec(const torch::Tensor& t, long n,
+                          torch::ScalarType dtype, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 1 && t.size(0) == n &&
+                  t.scalar_type() == dtype && t.is_contiguous(),
+              "lce: ", name, " must be a contiguous ", dtype,
+              " GPU vector [", n, "], got ", t.sizes(), " ", t.scalar_type());
+}
+
+// contiguous [rows, K] bf16 GPU matrix, base 16-byte aligned, K in range
+static void lce_check_mat(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.dim() == 2 &&
+                  t.scalar_type() == torch::kBFloat16,
+              "lce: ", name, " must be a 2-d bf16 GPU tensor, got ", t.sizes(),
+              " ", t.scalar_type());
+  long K = t.size(1);
+  TORCH_CHECK(K >= 32 && K % 32 == 0 && K <= LCE_MAX_K,
+              "lce: K must be a multiple of 32 in [32, ", LCE_MAX_K,
+              "], got ", K);
+  TORCH_CHECK(t.is_contiguous(), "lce: ", name, " must be contiguous");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, "lce: ",
+              name, " must be 16-byte aligned");
+}
+
+#define LCE_S(t) reinterpret_cast<short*>((t).data_ptr())
+
+// (h [N, K] bf16, labels [N] int64, ignore_index, M_cap) -> Hc [M_cap, K]
+// bf16, rows [M_cap] int64 (-1 pad), tgt [M_cap] int32 (-1 pad), count [1]
+// int32 on the device
+std::vector<torch::Tensor> lce_compact(torch::Tensor h, torch::Tensor labels,
+                                       long ignore_index, long M_cap) {
+  lce_check_mat(h, "h");
+  long N = h.size(0), K = h.size(1);
+  TORCH_CHECK(N >= 1 && N <= (1L << 24), "lce: 1 <= N <= 2^24, got ", N);
+  TORCH_CHECK(M_cap >= 1 && M_cap <= N, "lce: 1 <= M_cap <= N, got ", M_cap);
+  TORCH_CHECK(labels.scalar_type() == torch::kLong,
+              "lce: labels must be int64, got ", labels.scalar_type());
+  lce_check_vec(labels, N, torch::kLong, "labels");
+  auto hc = torch::empty({M_cap, K}, h.options());
+  auto rows = torch::empty({M_cap}, labels.options());
+  auto tgt = torch::empty({M_cap}, labels.options().dtype(torch::kInt32));
+  auto count = torch::empty({1}, labels.options().dtype(torch::kInt32));
+  hipLaunchKernelGGL(lce_scan_kernel, dim3(1), dim3(256), 0, cur_stream(),
+                     labels.data_ptr<long>(), ignore_index, (int)N, (int)M_cap,
+                     rows.data_ptr<long>(), tgt.data_ptr<int>(),
+                     count.data_ptr<int>());
+  long items = M_cap * (K / 8);
+  hipLaunchKernelGGL(lce_gather_kernel, dim3((unsigned)((items + 255) / 256)),
+                     dim3(256), 0, cur_stream(), LCE_S(h),
+                     rows.data_ptr<long>(), LCE_S(hc), (int)M_cap, (int)K);
+  return {hc, rows, tgt, count};
+}
+
+// shared operand checks of the forward and the backward; returns the bias
+// pointer (null without a bias)
+static const float* lce_check_main(const torch::Tensor& hc,
+                                   const torch::Tensor& w,
+                                   const c10::optional<torch::Tensor>& bias,
+                                   const torch::Tensor& rows,
+                                   const torch::Tensor& tgt,
+                                   const torch::Tensor& count) {
+  lce_check_mat(hc, "Hc");
+  lce_check_mat(w, "weight");
+  long M_cap = hc.size(0), V = w.size(0);
+  TORCH_CHECK(w.size(1) == hc.size(1), "lce: weight must be [V, ", hc.size(1),
+              "], got ", w.sizes());
+  TORCH_CHECK(V >= 2 && V < (1L << 30), "lce: 2 <= V < 2^30, got ", V);
+  TORCH_CHECK(M_cap >= 1 && M_cap <= (1L << 24),
+              "lce: 1 <= M_cap <= 2^24, got ", M_cap);
+  lce_check_vec(rows, M_cap, torch::kLong, "rows");
+  lce_check_vec(tgt, M_cap, torch::kInt32, "tgt");
+  lce_check_vec(count, 1, torch::kInt32, "count");
+  if (bias.has_value() && bias->defined()) {
+    lce_check_vec(*bias, V, torch::kFloat32, "bias");
+    return bias->data_ptr<float>();
+  }
+  return nullptr;
+}
+
+// (Hc, weight [V, K] bf16, bias [V] fp32 or None, rows, tgt, count, N) ->
+// loss [N] fp32 (zeros in rows that were not kept), stats [2] = (sum, mean
+// over the kept rows), lse2 [M_cap] (log2 domain)
+std::vector<torch::Tensor> lce_fwd(torch::Tensor hc, torch::Tensor w,
+                                   c10::optional<torch::Tensor> bias,
+                                   torch::Tensor rows, torch::Tensor tgt,
+                                   torch::Tensor count, long N) {
+  const float* bp = lce_check_main(hc, w, bias, rows, tgt, count);
+  long M_cap = hc.size(0), K = hc.size(1), V = w.size(0);
+  TORCH_CHECK(N >= M_cap, "lce_fwd: N must be at least M_cap");
+  long splits = (V + LCE_SPLIT_COLS - 1) / LCE_SPLIT_COLS;
+  long row_blocks = (M_cap + LCE_BM - 1) / LCE_BM;
+  long cblocks = (M_cap + 255) / 256;
+  auto fopt = hc.options().dtype(torch::kFloat32);
+  auto part = torch::empty({splits, M_cap, 2}, fopt);
+  // a target outside [0, V) is picked by no lane: its row's loss is NaN
+  auto zt = torch::full({M_cap}, std::numeric_limits<float>::quiet_NaN(), fopt);
+  auto loss = torch::zeros({N}, fopt);
+  auto lse2 = torch::empty({M_cap}, fopt);
+  auto blocksum = torch::empty({cblocks}, fopt);
+  auto stats = torch::empty({2}, fopt);
+  hipLaunchKernelGGL(lce_fwd_kernel,
+                     dim3((unsigned)row_blocks, (unsigned)splits), dim3(256),
+                     0, cur_stream(), LCE_S(hc), LCE_S(w), bp,
+                     tgt.data_ptr<int>(), count.data_ptr<int>(),
+                     part.data_ptr<float>(), zt.data_ptr<float>(), (int)M_cap,
+                     (int)V, (int)K);
+  hipLaunchKernelGGL(lce_combine_kernel, dim3((unsigned)cblocks), dim3(256),
+                     0, cur_stream(), part.data_ptr<float>(),
+                     zt.data_ptr<float>(), rows.data_ptr<long>(),
+                     count.data_ptr<int>(), loss.data_ptr<float>(),
+                     lse2.data_ptr<float>(), blocksum.data_ptr<float>(),
+                     (int)M_cap, (int)splits);
+  hipLaunchKernelGGL(lce_mean_kernel, dim3(1), dim3(256), 0, cur_stream(),
+                     blocksum.data_ptr<float>(), count.data_ptr<int>(),
+                     stats.data_ptr<float>(), (int)cblocks);
+  return {loss, stats, lse2};
+}
+
+// g_rows [N] fp32 (gradient of the loss rows) and / or g_mean [1] fp32
+// (gradient of the mean) -> dz [M_cap, V_ld] bf16, db [V] fp32 (column sums
+// of the unrounded dz; undefined without a bias)
+std::vector<torch::Tensor> lce_bwd(torch::Tensor hc, torch::Tensor w,
+                                   c10::optional<torch::Tensor> bias,
+                                   torch::Tensor rows, torch::Tensor tgt,
+                                   torch::Tensor count, torch::Tensor lse2,
+                                   c10::optional<torch::Tensor> g_rows,
+                                   c10::optional<torch::Tensor> g_mean) {
+  const float* bp = lce_check_main(hc, w, bias, rows, tgt, count);
+  long M_cap = hc.size(0), K = hc.size(1), V = w.size(0);
+  lce_check_vec(lse2, M_cap, torch::kFloat32, "lse2");
+  const float* grp = nullptr;
+  const float* gmp = nullptr;
+  if (g_rows.has_value() && g_rows->defined()) {
+    TORCH_CHECK(g_rows->dim() == 1 && g_rows->size(0) >= M_cap,
+                "lce_bwd: g_rows must be [N] with N >= M_cap");
+    lce_check_vec(*g_rows, g_rows->size(0), torch::kFloat32, "g_rows");
+    grp = g_rows->data_ptr<float>();
+  }
+  if (g_mean.has_value() && g_mean->defined()) {
+    lce_check_vec(*g_mean, 1, torch::kFloat32, "g_mean");
+    gmp = g_mean->data_ptr<float>();
+  }
+  long V_ld = (V + 7) / 8 * 8;
+  long splits = (V + LCE_SPLIT_COLS - 1) / LCE_SPLIT_COLS;
+  long row_blocks = (M_cap + LCE_BM - 1) / LCE_BM;
+  auto fopt = hc.options().dtype(torch::kFloat32);
+  auto dz = torch::empty({M_cap, V_ld}, hc.options());
+  torch::Tensor colpart, db;
+  if (bp) {
+    colpart = torch::empty({row_blocks, V_ld}, fopt);
+    db = torch::empty({V}, fopt);
+  }
+  hipLaunchKernelGGL(lce_bwd_kernel,
+                     dim3((unsigned)row_blocks, (unsigned)splits), dim3(256),
+                     0, cur_stream(), LCE_S(hc), LCE_S(w), bp,
+                     tgt.data_ptr<int>(), count.data_ptr<int>(),
+                     lse2.data_ptr<float>(), rows.data_ptr<long>(), grp, gmp,
+                     LCE_S(dz), bp ? colpart.data_ptr<float>() : nullptr,
+                     (int)M_cap, (int)V, (int)V_ld, (int)K);
+  if (bp)
+    hipLaunchKernelGGL(lce_dbias_kernel, dim3((unsigned)((V + 255) / 256)),
+                       dim3(256), 0, cur_stream(), colpart.data_ptr<float>(),
+                       count.data_ptr<int>(), db.data_ptr<float>(), (int)V,
+                       (int)V_ld, (int)row_blocks);
+  return {dz, db};
+}
+#undef LCE_S
+
 // ---- fused NeuMF (ncf_ops.hip) ----
 
 static void neumf_check_f32(const torch::Tensor& t, const torch::Tensor& ids,
@@ -2236,6 +2406,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.attr("SSM_BN") = SSM_BN;
   m.attr("SSM_SPLIT_COLS") = SSM_SPLIT_COLS;
   m.attr("SSM_MAX_P") = SSM_MAX_P;
+  m.def("lce_compact", &lce_compact,
+        "linear + cross-entropy: (h [N, K] bf16, labels [N], ignore_index, "
+        "M_cap) -> (Hc [M_cap, K] bf16, rows, tgt, count [1] on the device)");
+  m.def("lce_fwd", &lce_fwd,
+        "linear + cross-entropy forward on bf16 MFMA: (Hc, weight, bias or "
+        "None, rows, tgt, count, N) -> (loss [N], (sum, mean) [2], lse2 "
+        "[M_cap])");
+  m.def("lce_bwd", &lce_bwd,
+        "linear + cross-entropy backward: (Hc, weight, bias or None, rows, "
+        "tgt, count, lse2, g_rows [N] or None, g_mean [1] or None) -> (dz "
+        "[M_cap, V_ld] bf16, db [V] or None)");
+  // lce tiling: vocabulary columns per split
+  m.attr("LCE_SPLIT_COLS") = LCE_SPLIT_COLS;
   m.def("neumf_fwd", &neumf_fwd,
         "fused NeuMF forward on fp32 MFMA: (users, items, [mf_user, mf_item, "
         "mlp_user, mlp_item], MLP weights, MLP biases, head weight, head "
