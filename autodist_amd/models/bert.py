@@ -8,8 +8,8 @@ masked-LM head (weight-tied). BASELINE config #3 is BERT-base Parallax on
 embedding tables go to load-balanced PS owners.
 
 Attention runs the fused MFMA kernels (ops/fused_attention.py; torch SDPA
-where they do not apply), LayerNorm and the Linear bias gradients their HIP
-kernels, and the masked-LM loss the fused linear + cross-entropy kernels
+where they do not apply), hidden dropout + residual + LayerNorm and the
+Linear bias gradients their HIP kernels, and the masked-LM loss the fused linear + cross-entropy kernels
 (ops/fused_linear_ce.py), which compute only the labelled positions and
 never store the logits. Params stay fp32 with bf16 autocast compute.
 """
@@ -87,10 +87,12 @@ class BertLayer(nn.Module):
         self.drop = nn.Dropout(cfg.dropout)
 
     def forward(self, x, attn_mask=None):
-        # residual adds fold into the fused bf16 LN kernels (gfx950)
-        x = self.ln1(self.drop(self.attn(x, attn_mask)), residual=x)
+        # hidden dropout and residual adds fold into the fused bf16 LN
+        # kernels (gfx950); self.drop only carries p
+        p = self.drop.p
+        x = self.ln1(self.attn(x, attn_mask), residual=x, dropout_p=p)
         h = self.fc2(torch.nn.functional.gelu(self.fc1(x)))
-        return self.ln2(self.drop(h), residual=x)
+        return self.ln2(h, residual=x, dropout_p=p)
 
 
 class BertModel(nn.Module):

@@ -37,20 +37,8 @@ __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_wave_barrier();
 }
 
-// counter-based dropout hash: uniform in [0, 2^32); keep iff >= p*2^32.
-// Pure function of (seed, bh, q, k) so forward and both backward kernels
-// regenerate the identical mask.
-__device__ __forceinline__ unsigned int drop_hash(unsigned int seed,
-                                                  unsigned int bh,
-                                                  unsigned int q,
-                                                  unsigned int k) {
-  unsigned int x = seed ^ (bh * 0x9E3779B9u) ^ (q * 0x85EBCA6Bu)
-                   ^ (k * 0xC2B2AE35u);
-  x ^= x >> 16; x *= 0x7FEB352Du;
-  x ^= x >> 15; x *= 0x846CA68Bu;
-  x ^= x >> 16;
-  return x;
-}
+// dropout: drop_hash (common.h), a pure function of (seed, bh, q, k), so
+// forward and both backward kernels regenerate the identical mask.
 
 // 256 threads (4 waves); each wave owns RB x 16 query rows, so a block
 // covers 64*RB queries. K/V tiles are shared by all 4 waves from LDS, so

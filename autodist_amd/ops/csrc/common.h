@@ -69,3 +69,24 @@ __device__ __forceinline__ float dpp16_max(float v) {
 }
 
 #define ATTN_LOG2E 1.4426950408889634f
+
+// counter-based dropout hash: uniform in [0, 2^32); keep iff >= p*2^32.
+// Shared by the attention kernels (bh, q, k) and the dropout + LayerNorm
+// kernels (0, row, col): integer-only, so any kernel regenerates a mask from
+// its seed instead of storing it.
+__device__ __forceinline__ unsigned int drop_hash(unsigned int seed,
+                                                  unsigned int bh,
+                                                  unsigned int q,
+                                                  unsigned int k) {
+  unsigned int x = seed ^ (bh * 0x9E3779B9u) ^ (q * 0x85EBCA6Bu)
+                   ^ (k * 0xC2B2AE35u);
+  x ^= x >> 16; x *= 0x7FEB352Du;
+  x ^= x >> 15; x *= 0x846CA68Bu;
+  x ^= x >> 16;
+  return x;
+}
+
+// keep iff drop_hash(...) >= drop_thresh(p)
+__device__ __forceinline__ unsigned int drop_thresh(float p_drop) {
+  return (unsigned int)fminf(p_drop * 4294967296.0f, 4294967040.0f);
+}

@@ -1489,6 +1489,135 @@ std::vector<torch::Tensor> ln_bwd(torch::Tensor dy, torch::Tensor u,
   return {dx, gb[0], gb[1]};
 }
 
+// ---- fused dropout + residual + LayerNorm (ln_drop_* kernels) ----
+static bool lnd_aligned16(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+static void lnd_check_rows(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 &&
+              t.dim() >= 1 && t.is_contiguous() && lnd_aligned16(t),
+              name, ": contiguous 16-byte aligned bf16 GPU tensor expected");
+  long H = t.size(-1);
+  TORCH_CHECK(H % 8 == 0 && H >= 8 && H <= 4096, name,
+              ": the ln_drop kernels serve H % 8 == 0, 8 <= H <= 4096, got ",
+              H);
+  TORCH_CHECK(t.numel() / H < (1L << 31), name, ": too many rows");
+}
+
+static void lnd_check_vec(const torch::Tensor& t, long n, bool aligned,
+                          const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
+              t.is_contiguous() && t.numel() == n &&
+              (!aligned || lnd_aligned16(t)),
+              name, ": contiguous fp32 GPU tensor of ", n, " elements ",
+              "expected");
+}
+
+// lane-group geometry from H / 8 vectors per row (see ln_ops.hip)
+#define LND_DISPATCH(H8, CALL)                                            \
+  do {                                                                    \
+    if ((H8) <= 64) { CALL(64, 1); }                                      \
+    else if ((H8) <= 128) { CALL(128, 1); }                               \
+    else if ((H8) <= 256) { CALL(256, 1); }                               \
+    else { CALL(256, 2); }                                                \
+  } while (0)
+
+static long lnd_rows_per_block(long H8) {
+  return H8 <= 64 ? 4 : H8 <= 128 ? 2 : 1;
+}
+
+std::vector<torch::Tensor> ln_drop_fwd(torch::Tensor x,
+                                       c10::optional<torch::Tensor> res,
+                                       torch::Tensor gamma,
+                                       torch::Tensor beta, double eps,
+                                       double p, int64_t seed) {
+  lnd_check_rows(x, "ln_drop_fwd x");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "ln_drop_fwd: 0 <= p < 1, got ", p);
+  long H = x.size(-1);
+  long N = x.numel() / H;
+  bool has_res = res.has_value() && res->defined();
+  if (has_res) {
+    lnd_check_rows(*res, "ln_drop_fwd res");
+    TORCH_CHECK(res->sizes() == x.sizes(), "ln_drop_fwd: res shape != x");
+  }
+  // gamma / beta may be views into a flat parameter buffer: any 4-byte
+  // alignment is served, 16 bytes gets the float4 loads
+  lnd_check_vec(gamma, H, false, "ln_drop_fwd gamma");
+  lnd_check_vec(beta, H, false, "ln_drop_fwd beta");
+  bool gvec = lnd_aligned16(gamma) && lnd_aligned16(beta);
+  auto y = torch::empty_like(x);
+  auto u = torch::empty_like(x);
+  auto fopt = x.options().dtype(torch::kFloat32);
+  auto mean = torch::empty({N}, fopt);
+  auto rstd = torch::empty({N}, fopt);
+  if (N == 0) return {y, u, mean, rstd};
+  const __hip_bfloat16* rp = has_res
+      ? reinterpret_cast<__hip_bfloat16*>(res->data_ptr()) : nullptr;
+  long H8 = H / 8, rpb = lnd_rows_per_block(H8);
+#define LND_FWD(G, V)                                                     \
+  hipLaunchKernelGGL((ln_drop_fwd_kernel<G, V>), dim3((N + rpb - 1) / rpb), \
+                     dim3(256), 0, cur_stream(),                          \
+                     reinterpret_cast<__hip_bfloat16*>(x.data_ptr()), rp, \
+                     gamma.data_ptr<float>(), beta.data_ptr<float>(),     \
+                     reinterpret_cast<__hip_bfloat16*>(y.data_ptr()),     \
+                     reinterpret_cast<__hip_bfloat16*>(u.data_ptr()),     \
+                     mean.data_ptr<float>(), rstd.data_ptr<float>(), N,   \
+                     (int)H, (float)eps, (float)p,                        \
+                     (unsigned int)(uint64_t)seed, gvec)
+  LND_DISPATCH(H8, LND_FWD);
+#undef LND_FWD
+  return {y, u, mean, rstd};
+}
+
+std::vector<torch::Tensor> ln_drop_bwd(torch::Tensor dy, torch::Tensor u,
+                                       torch::Tensor gamma,
+                                       torch::Tensor mean, torch::Tensor rstd,
+                                       double p, int64_t seed) {
+  lnd_check_rows(dy, "ln_drop_bwd dy");
+  lnd_check_rows(u, "ln_drop_bwd u");
+  TORCH_CHECK(u.sizes() == dy.sizes(), "ln_drop_bwd: u shape != dy");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "ln_drop_bwd: 0 <= p < 1, got ", p);
+  long H = dy.size(-1);
+  long N = dy.numel() / H;
+  lnd_check_vec(gamma, H, false, "ln_drop_bwd gamma");
+  bool gvec = lnd_aligned16(gamma);
+  lnd_check_vec(mean, N, false, "ln_drop_bwd mean");
+  lnd_check_vec(rstd, N, false, "ln_drop_bwd rstd");
+  auto dx = torch::empty_like(dy);
+  auto dres = torch::empty_like(dy);
+  auto fopt = dy.options().dtype(torch::kFloat32);
+  if (N == 0) {
+    auto z = torch::zeros({2, H}, fopt);
+    return {dx, dres, z[0], z[1]};
+  }
+  long H8 = H / 8, rpb = lnd_rows_per_block(H8);
+  // a function of (N, H) alone: a block walks several rows, ascending
+  long nb = std::min<long>((N + rpb - 1) / rpb, LND_BWD_GRID_MAX);
+  auto partials = torch::empty({nb, 2, H}, fopt);
+  auto gb = torch::empty({2, H}, fopt);
+#define LND_BWD(G, V)                                                     \
+  hipLaunchKernelGGL((ln_drop_bwd_kernel<G, V>), dim3(nb), dim3(256), 0,  \
+                     cur_stream(),                                        \
+                     reinterpret_cast<__hip_bfloat16*>(dy.data_ptr()),    \
+                     reinterpret_cast<__hip_bfloat16*>(u.data_ptr()),     \
+                     gamma.data_ptr<float>(), mean.data_ptr<float>(),     \
+                     rstd.data_ptr<float>(),                              \
+                     reinterpret_cast<__hip_bfloat16*>(dx.data_ptr()),    \
+                     reinterpret_cast<__hip_bfloat16*>(dres.data_ptr()),  \
+                     partials.data_ptr<float>(), N, (int)H, (float)p,     \
+                     (unsigned int)(uint64_t)seed, gvec)
+  LND_DISPATCH(H8, LND_BWD);
+#undef LND_BWD
+  long H2 = 2 * H;
+  hipLaunchKernelGGL(ln_drop_gb_finalize_kernel,
+                     dim3((H2 + LND_FIN_COLS - 1) / LND_FIN_COLS),
+                     dim3(LND_FIN_COLS * LND_FIN_SLICES), 0, cur_stream(),
+                     partials.data_ptr<float>(), gb.data_ptr<float>(),
+                     (int)nb, (int)H2);
+  return {dx, dres, gb[0], gb[1]};
+}
+
 torch::Tensor col_sum(torch::Tensor x) {
   TORCH_CHECK(x.dim() == 2 && x.scalar_type() == torch::kBFloat16 &&
               x.is_contiguous());
@@ -2438,6 +2567,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused bf16 LayerNorm(+residual) forward -> y, u, mean, rstd");
   m.def("ln_bwd", &ln_bwd, "fused bf16 LayerNorm backward -> dx, dgamma, "
         "dbeta");
+  m.def("ln_drop_fwd", &ln_drop_fwd,
+        "fused dropout + residual + bf16 LayerNorm forward, "
+        "y = LN(dropout_p(x) + res) with the hash mask of seed "
+        "-> y, u, mean, rstd",
+        py::arg("x"), py::arg("res"), py::arg("gamma"), py::arg("beta"),
+        py::arg("eps"), py::arg("p"), py::arg("seed"));
+  m.def("ln_drop_bwd", &ln_drop_bwd,
+        "one-pass backward of ln_drop_fwd (mask regenerated from seed) "
+        "-> dx, dres, dgamma, dbeta",
+        py::arg("dy"), py::arg("u"), py::arg("gamma"), py::arg("mean"),
+        py::arg("rstd"), py::arg("p"), py::arg("seed"));
   m.def("attn_dropmask", &attn_dropmask,
         "materialize the hash dropout keep-mask (testing)");
   m.def("attn_fwd", &attn_fwd,
